@@ -26,7 +26,7 @@ by rank): buckets are independent (core.cpp:1052-1087), so the path shards
 with no collective; "scaling": "weak", value = all ranks' bytes / the slowest
 rank's time, and per_rank_GBps lists each rank's rate.
 
-Every N also carries a ``c4`` sub-object (BASELINE.json configs[3]): the
+With ``--full`` every N also carries a ``c4`` sub-object (BASELINE.json configs[3]): the
 1,024-bucket stream (256 KiB - 64 MiB, log-uniform, seeded: shard.c4_sizes)
 sharded over the N ranks by shard.ShardPlan (key-affine, bytes-balanced), one
 sweep = every bucket once in batched launches of <= 32 on four streams; the
@@ -38,7 +38,22 @@ GPU).  RCCL carries only the timing barriers and the max / sum reductions.
 ``--backend oracle`` rehearses the multi-rank path on CPU (gloo; the CPU
 restatement stands in for the device; small sizes) for tests/test_bench_cli.py.
 
-Extra fields: ``roofline`` for the dominant (only) kernel, tv16_batch, timed
+A plain run does what the headline needs and no more: it sets up, warms up,
+times the ``--steps`` steps, writes its outputs if ``--dump-outputs DIR`` is
+given, and prints the result line (``ms_per_step`` = the timed region over
+``--steps``).  The clock warm-up (``--warmup-seconds``) steps a twin codec
+handle with its own AIMD state on the same buckets, so the measured handle has
+made exactly 1 + warmup calls per key when the timed region starts and its
+output does not depend on how many steps fitted into the warm-up time.
+``--dump-outputs DIR`` writes what the last timed step returned to its caller,
+every key's stream in key order: DIR/indices.npy (float64), DIR/values.npy
+(float32) -- a fixed, seeded, sorted sample of 2 Mi positions of the
+concatenated streams where they hold more, the positions in DIR/positions.npy
+(float64) -- and DIR/counts.npy (float64, one per key); with N > 1 each rank writes
+``<name>_rank<r>.npy``.  Equal arguments give equal inputs on every run.
+
+``--full`` adds everything else: the ``c4`` sub-object above, and the extra
+fields ``roofline`` for the dominant (only) kernel, tv16_batch, timed
 live with HIP events over the profiled steps on stream 0, the other streams
 joined to it (algorithmic bytes = 4n + 8k per bucket; achieved = those bytes
 over the interval; pitch_us = interval x concurrent launches / launches, the
@@ -103,6 +118,11 @@ def parse():
                    help="scale each (key, set) bucket by a seeded factor in [1 - J, 1 + J] (gradient-scale "
                         "noise: AIMD window misses at a realistic rate)")
     p.add_argument("--master-port", type=int, default=29517)
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="write what the last timed step returned (indices, values, counts) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: the c4 sub-object, the live roofline "
+                        "timing, the committed profile summaries and the CPU baseline")
     return p.parse_args()
 
 
@@ -189,6 +209,23 @@ def jitter_factor(bucket: int, par: int, jitter: float) -> float:
     from stellatrain_amd.synth import _splitmix64, seed_for
     r = int(_splitmix64(np.array([seed_for(bucket, par) ^ 0x7A11], np.uint64))[0]) >> 11
     return float(1.0 + jitter * (2.0 * r / float(1 << 53) - 1.0))
+
+
+DUMP_SAMPLE = 1 << 21  # positions of the concatenated streams kept by --dump-outputs (20 B each: 40 MiB)
+
+
+def dump_outputs(dirname, world, rank, idx, val, counts):
+    """What the last timed step handed its caller: the streams of all keys
+    back to back (idx, val: host arrays of sum(k) entries) and each key's
+    count.  Larger outputs are cut to a fixed, seeded, sorted sample."""
+    os.makedirs(dirname, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    pos = np.arange(idx.size, dtype=np.int64)
+    if idx.size > DUMP_SAMPLE:
+        pos = np.sort(np.random.default_rng(0x5EED).choice(idx.size, DUMP_SAMPLE, replace=False))
+    for name, a in (("indices", idx[pos].astype(np.float64)), ("values", val[pos].astype(np.float32)),
+                    ("positions", pos.astype(np.float64)), ("counts", np.asarray(counts, np.float64))):
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), a)
 
 
 def fill_profile():
@@ -367,6 +404,7 @@ def main():
     nb = len(items)
     ns = max(1, min(args.streams, nb))
     comp = make_compressor(args.method, device=local)
+    heat = make_compressor(args.method, device=local)  # the clock warm-up's handle: its own per-key state
     stream = torch.cuda.current_stream(dev)
     streams = [stream] + [torch.cuda.Stream(dev) for _ in range(ns - 1)]
 
@@ -406,9 +444,9 @@ def main():
             calls.append((comp.bucket_array(rows), len(rows), streams[j % ns].cuda_stream))
         plans.append(calls)
 
-    def step(s):
+    def step(s, c=comp):
         for arr, n_, sp in plans[s % nsets]:
-            comp.compress_batch_raw(arr, n_, sp)
+            c.compress_batch_raw(arr, n_, sp)
 
     def sync_streams():
         for st in streams[1:]:
@@ -425,14 +463,16 @@ def main():
         step(s + 1)
     sync_streams()
     # the GPU holds low clocks for a while after going busy: keep stepping
-    # until --warmup-seconds have passed before anything is timed
+    # until --warmup-seconds have passed before anything is timed (on the twin
+    # handle: the measured handle's call history stays 1 + warmup per key)
     t0 = time.perf_counter()
     s = args.warmup + 1
     while time.perf_counter() - t0 < args.warmup_seconds:
         for _ in range(4):
-            step(s)
+            step(s, heat)
             s += 1
         sync_streams()
+    heat.check_device()
 
     # ---- timed region ----
     if world > 1:
@@ -454,27 +494,29 @@ def main():
     comp.check_device()
     if not os.environ.get("STG_DEBUG_TV16_STAGE"):  # diagnostic stages skip the fill
         assert bool((counts[:nb].cpu().numpy() == np.array(ks, np.int32)).all()), "count != dst_len"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, world, rank, oidx[:sum(ks)].cpu().numpy().view(np.uint32),
+                     oval[:sum(ks)].cpu().numpy(), counts[:nb].cpu().numpy())
 
-    # ---- live kernel timing (HIP events, no per-launch instrumentation) ----
+    # ---- live kernel timing (--full; HIP events, no per-launch instrumentation) ----
     # events on stream 0 bracketing the profile steps of all streams: with S
     # streams, S launches overlap, so algorithmic bytes / interval is the
     # chip's rate and S x interval / launches the per-launch duration
     # rocprofv3 reports.
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    ev0.record(stream)
-    for st in streams[1:]:
-        st.wait_event(ev0)
-    for s in range(args.profile_steps):
-        step(s)
-    for st in streams[1:]:
-        stream.wait_stream(st)
-    ev1.record(stream)
-    torch.cuda.synchronize()
-    chip_ms = ev0.elapsed_time(ev1)
-    launches = args.profile_steps * len(groups)
-    conc = min(ns, len(groups))
-    pitch_us = chip_ms * 1e3 * conc / max(launches, 1)
+    def profile_interval_ms():
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        ev0.record(stream)
+        for st in streams[1:]:
+            st.wait_event(ev0)
+        for s in range(args.profile_steps):
+            step(s)
+        for st in streams[1:]:
+            stream.wait_stream(st)
+        ev1.record(stream)
+        torch.cuda.synchronize()
+        return ev0.elapsed_time(ev1)
+    chip_ms = profile_interval_ms() if args.full else None
 
     my_bytes = 4.0 * tot
     all_bytes = torch.tensor([my_bytes], dtype=torch.float64, device=dev)
@@ -486,15 +528,13 @@ def main():
         per_rank_gbps = [round(float(r.item()), 2) for r in rates]
     total_bytes = float(all_bytes.item()) * args.steps
     value = total_bytes / el / 1e9
-    alg_step = sum(4.0 * n + 8.0 * k for _, n, k, _ in items)  # 4n + 8k per bucket
-    achieved = alg_step * args.profile_steps / (chip_ms * 1e-3) / 1e9
     shard_meta = None
     if world > 1:
         gathered = [None] * world
         dist.all_gather_object(gathered, {"rank": rank, "buckets": [b for *_, b in items], "bytes": my_bytes})
         shard_meta = gathered
     c4 = None
-    if wl == "headline" and args.c4_sweeps > 0:
+    if args.full and wl == "headline" and args.c4_sweeps > 0:
         del sets
         torch.cuda.empty_cache()
         c4 = c4_measure(args, world, rank, comp, streams, dist)
@@ -518,19 +558,6 @@ def main():
                        if args.jitter > 0 else "") + ", device resident)",
             "config": dict(desc, streams=ns, buckets_per_launch=round(per_launch, 2),
                            parallelism=f"bucket-sharded x{world}, no collective"),
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "traffic": load_traffic(per_launch) if wl == "headline" else None,
-                         "kernel": "tv16_batch", "alg_bytes_per_launch": int(alg_step / max(len(groups), 1)),
-                         "pitch_us": round(pitch_us, 2), "concurrent_launches": conc, "launches_timed": int(launches),
-                         "interval_us": round(chip_ms * 1e3, 1), "rank": 0,
-                         "basis": "step-level: algorithmic bytes of the profiled steps over their chip interval "
-                                  "(HIP events on stream 0, the other streams joined); the per-launch kernel "
-                                  "durations overlap (concurrent_launches in flight), so a per-kernel figure "
-                                  "cannot reproduce this frac",
-                         # the same algorithmic bytes over the timed region's wall clock (the clock
-                         # `value` uses, barriers and the last launches' drain included), per GPU
-                         "frac_timed_region": round(alg_step * args.steps / el / 1e9 / HBM_PEAK_GBS, 4)},
             "per_gpu_GBps": round(value / world, 2),
             "per_rank_GBps": per_rank_gbps,
             "rccl_world_size": dist.get_world_size() if world > 1 else 1,
@@ -543,12 +570,32 @@ def main():
                              for g in shard_meta]
             if args.dump_shards:
                 json.dump(shard_meta, open(args.dump_shards, "w"))
-        fp = fill_profile() if wl == "headline" else None
-        if fp:
-            out["fill_profile"] = fp
+        if args.full:
+            alg_step = sum(4.0 * n + 8.0 * k for _, n, k, _ in items)  # 4n + 8k per bucket
+            achieved = alg_step * args.profile_steps / (chip_ms * 1e-3) / 1e9
+            launches = args.profile_steps * len(groups)
+            conc = min(ns, len(groups))
+            pitch_us = chip_ms * 1e3 * conc / max(launches, 1)
+            out["roofline"] = {
+                "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 4),
+                "traffic": load_traffic(per_launch) if wl == "headline" else None,
+                "kernel": "tv16_batch", "alg_bytes_per_launch": int(alg_step / max(len(groups), 1)),
+                "pitch_us": round(pitch_us, 2), "concurrent_launches": conc, "launches_timed": int(launches),
+                "interval_us": round(chip_ms * 1e3, 1), "rank": 0,
+                "basis": "step-level: algorithmic bytes of the profiled steps over their chip interval "
+                         "(HIP events on stream 0, the other streams joined); the per-launch kernel "
+                         "durations overlap (concurrent_launches in flight), so a per-kernel figure "
+                         "cannot reproduce this frac",
+                # the same algorithmic bytes over the timed region's wall clock (the clock
+                # `value` uses, barriers and the last launches' drain included), per GPU
+                "frac_timed_region": round(alg_step * args.steps / el / 1e9 / HBM_PEAK_GBS, 4)}
+            fp = fill_profile() if wl == "headline" else None
+            if fp:
+                out["fill_profile"] = fp
         if c4 is not None:
             out["c4"] = c4
-        if world == 1 and not args.no_cpu_baseline and wl == "headline":
+        if args.full and world == 1 and not args.no_cpu_baseline and wl == "headline":
             out["cpu_baseline"] = cpu_baseline(items[0][1], items[0][2], args.cpu_seconds)
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -572,24 +619,28 @@ def main_oracle(args, world, rank):
     o = Oracle()
     h = o.tv16_new()
 
-    def timed(items_, steps):
+    def timed(items_, steps, dump=""):
         nsets = max(1, args.sets)
         data = [[o.synth(n, seed_for(b, par)) * np.float32(jitter_factor(b, par, args.jitter) if args.jitter > 0 else 1)
                  for (_, n, _, b) in items_] for par in range(nsets)]
 
         def step(s):
-            return [o.tv16_compress(h, key, data[s % nsets][j], k)[0] for j, (key, _, k, _) in enumerate(items_)]
+            return [o.tv16_compress(h, key, data[s % nsets][j], k) for j, (key, _, k, _) in enumerate(items_)]
         step(0)
         for s in range(args.warmup):
             step(s + 1)
         if world > 1:
             dist.barrier()
         t0 = time.perf_counter()
-        cnt = None
+        res = None
         for s in range(steps):
-            cnt = step(s)
+            res = step(s)
         el = time.perf_counter() - t0
+        cnt = [c for c, _, _ in res]
         assert cnt == [k for _, _, k, _ in items_]
+        if dump:
+            dump_outputs(dump, world, rank, np.concatenate([i[:c] for c, i, _ in res]).view(np.uint32),
+                         np.concatenate([v[:c] for c, _, v in res]), cnt)
         mine = torch.tensor([el, 4.0 * sum(n for _, n, _, _ in items_)], dtype=torch.float64)
         if world > 1:
             allr = [torch.zeros(2, dtype=torch.float64) for _ in range(world)]
@@ -600,10 +651,10 @@ def main_oracle(args, world, rank):
         total = sum(float(t[1]) for t in allr)
         return total * steps / slow / 1e9, slow, [round(float(t[1]) * steps / float(t[0]) / 1e9, 4) for t in allr]
 
-    value, slow, per_rank = timed(items, args.steps)
+    value, slow, per_rank = timed(items, args.steps, args.dump_outputs)
     c4 = None
     gathered = []
-    if wl == "headline" and args.c4_sweeps > 0:
+    if args.full and wl == "headline" and args.c4_sweeps > 0:
         sizes = c4_sizes(args.c4_count, args.c4_lo, args.c4_hi)
         plan = ShardPlan(sizes, world)
         c4_items = [(plan.key(b), sizes[b], merge_numel(sizes[b], args.ratio, 1), b) for b in plan.local(rank)]
