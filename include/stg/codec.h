@@ -210,6 +210,31 @@ int stg_sgd_optimize_raw_device(stg_sgd_t o, const char *name, float *d_param, u
                                 const float *d_grad, const uint32_t *d_idx, uint32_t grad_len,
                                 const uint32_t *d_grad_len, void *stream);
 int stg_sgd_get_momentum(stg_sgd_t o, const char *name, float *host_out, uint32_t len, void *stream);
+/* Smart momentum, SGD::configure("smart_momentum", bool) (sgd.cpp:291-292):
+ * an element's buffer decays by pow(momentum, iterations since its index was
+ * last touched) instead of by momentum (sgd.cpp:225-227, 258-259).  The
+ * iteration count belongs to the handle, not to a name: every optimize_raw /
+ * merge_optimize call advances it, whatever the name and even with no
+ * gradients (sgd.cpp:262).  Legal at any time; a name's last-touched array is
+ * created zeroed by the first call that runs with the option on (the
+ * reference's stays zero while the option is off).  The factors are a table
+ * computed by the host's libm when the option is first enabled and kept on the
+ * device until destroy.  STG_ERR_INVALID unless 0 < momentum < 1 (the
+ * reference reads a null array at momentum 0 and asserts on factors outside
+ * [0, 1)); STG_ERR_UNSUPPORTED when the table would pass 2^22 entries (momentum
+ * above ~0.99997).  An index repeated within one call at an iteration > 0 has
+ * the factor pow(momentum, 0) == 1, on which the reference asserts: that
+ * element is skipped and the handle's failure word set (stg_sgd_check). */
+int stg_sgd_set_smart_momentum(stg_sgd_t o, int on);
+/* The name's last-touched iterations (min(len, param_len) words) after
+ * synchronising `stream`; STG_ERR_INVALID before the name's first call with
+ * the option on. */
+int stg_sgd_get_last(stg_sgd_t o, const char *name, uint32_t *host_out, uint32_t len, void *stream);
+/* The handle's iteration count: calls made so far (m_iter). */
+int stg_sgd_get_iter(stg_sgd_t o, uint32_t *out);
+/* Synchronises `stream` and reports the handle's sticky device failure word:
+ * STG_ERR_DEVICE if a smart-momentum element was ever skipped, else STG_OK. */
+int stg_sgd_check(stg_sgd_t o, void *stream);
 /* ModuleCpuOptimize::run (engine/modules/cpu_optimize.cpp:26-100): the MERGE
  * decompress of the received stream (as stg_scatter_merge_device: d_out_idx /
  * d_out_val / d_out_count get the merged stream, param_len is n) followed by

@@ -63,6 +63,10 @@ _SIGS = {
     "stg_sgd_optimize_raw_device": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                               C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "stg_sgd_get_momentum": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "stg_sgd_set_smart_momentum": (C.c_int, [C.c_void_p, C.c_int]),
+    "stg_sgd_get_last": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "stg_sgd_get_iter": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "stg_sgd_check": (C.c_int, [C.c_void_p, C.c_void_p]),
     "stg_merge_optimize_sgd_device": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                                 C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

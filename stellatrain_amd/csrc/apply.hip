@@ -26,6 +26,9 @@
 //   momentum:  b = first ? g : fmaf(b_old, m, (1-d)*g)   (vfmadd231ss, :242)
 //   nesterov:  g = fmaf(m, b, g)  else g = b             (vfmadd231ss, :247)
 //   update:    x = (float)fma(-lr, (double)g, (double)x) (vfnmadd231sd, :256)
+//   smart momentum (:54, 225-232, 258-259): m above is the element's factor
+//   (float)pow((double)m, (double)(m_iter - last[idx])) (m itself at m_iter 0),
+//   read from a table the host's libm filled; last[idx] = m_iter afterwards.
 //
 // Sparse Adam: optim/adam.cpp:19-86, shapes from the -O3 object code (see
 // oracle/stg_oracle.cpp adam_apply for the derivation):
@@ -316,14 +319,33 @@ __global__ void __launch_bounds__(STG_WG) win_emit1(const uint32_t *__restrict__
 // SGD::optimize_raw on one element (optim/sgd.cpp:34-263, scalar path), with
 // param[id] = x and mom[id] = m loaded by the caller: the same expression as
 // sgd_apply, so a step fused into the emission agrees with it bitwise.
-__device__ __forceinline__ void sgd_step(const SgdLaunch &a, uint32_t id, float g, float x, float m) {
+//
+// SMART (smart momentum, sgd.cpp:225-232, 258-259): `f` stands where the
+// momentum stands, f = sgd_factor(a, last[id]); an element whose factor is
+// outside [0, 1) -- the reference's assertion: the index was already touched
+// in this call -- is skipped and flagged.
+template <bool SMART>
+__device__ __forceinline__ float sgd_factor(const SgdLaunch &a, uint32_t last) {
+    if (!SMART || a.iter == 0) return a.momentum;
+    const uint32_t d = a.iter - last;
+    return a.pow_tab[d < a.pow_len ? d : a.pow_len - 1];  // past the table: its last entry, 0
+}
+
+template <bool SMART>
+__device__ __forceinline__ void sgd_step(const SgdLaunch &a, uint32_t id, float g, float x, float m, float f,
+                                         uint32_t last) {
+    if (SMART && a.iter != 0 && last == a.iter) {
+        g_or(a.fail, SGD_FAIL_FACTOR);
+        return;
+    }
     if (a.weight_decay != 0.f) g = fmaf(a.weight_decay, x, g);
     if (a.mom) {
-        const float b = a.first ? g : fmaf(m, a.momentum, (1.0f - a.dampening) * g);
-        g = a.nesterov ? fmaf(a.momentum, b, g) : b;
+        const float b = a.first ? g : fmaf(m, f, (1.0f - a.dampening) * g);
+        g = a.nesterov ? fmaf(f, b, g) : b;
         a.mom[id] = b;
     }
     a.param[id] = (float)fma(-a.lr, (double)g, (double)x);
+    if (SMART) a.last[id] = a.iter;
 }
 
 // Adam::optimize_raw on one element (optim/adam.cpp:19-86, no amsgrad), with
@@ -365,7 +387,8 @@ struct Win1Args {
 // WP pairs per lane: 4 (the default; 1,024-pair tiles, four times the
 // workgroups and the gathers of 16) or 16 (4,096-pair tiles: 41 workgroups at
 // 167,772 pairs, 13 us per call in the C5 kernel trace).
-template <uint32_t WP>
+// SMART: the fused SGD step with smart momentum (a.sgd.last set).
+template <uint32_t WP, bool SMART>
 __global__ void __launch_bounds__(STG_WG) win_emit1t(Win1Args a) {
     __shared__ uint32_t sh[STG_WAVES + 1];
     __shared__ uint32_t s_tile, s_bad;
@@ -398,12 +421,18 @@ __global__ void __launch_bounds__(STG_WG) win_emit1t(Win1Args a) {
             }
         }
         float xp[WP], mp[WP], vp[WP];
+        uint32_t lp[WP];  // SMART: the winners' last-touched words, then their factors in vp
         if (a.fuse_sgd) {  // every pair is a winner: its parameter and momentum words, loaded together
 #pragma unroll
             for (uint32_t b = 0; b < WP; ++b) {
                 const uint32_t id = e + b < a.m ? j[b] : 0u;
                 xp[b] = a.sgd.param[id];
                 mp[b] = a.sgd.mom ? a.sgd.mom[id] : 0.f;
+                lp[b] = SMART ? a.sgd.last[id] : 0u;
+            }
+            if (SMART) {  // the factors, gathered from the table together
+#pragma unroll
+                for (uint32_t b = 0; b < WP; ++b) vp[b] = sgd_factor<SMART>(a.sgd, lp[b]);
             }
         } else if (a.fuse_adam) {
 #pragma unroll
@@ -420,7 +449,8 @@ __global__ void __launch_bounds__(STG_WG) win_emit1t(Win1Args a) {
                 const float g = (0.0f + v[b]) / 1.0f;  // merged_grad[j] (cpu_optimize.cpp:49-55), world 1
                 a.out_idx[e + b] = j[b];
                 a.out_val[e + b] = g;
-                if (a.fuse_sgd) sgd_step(a.sgd, j[b], g, xp[b], mp[b]);  // indices unique: updates commute
+                if (a.fuse_sgd)  // indices unique: updates commute
+                    sgd_step<SMART>(a.sgd, j[b], g, xp[b], mp[b], SMART ? vp[b] : a.sgd.momentum, lp[b]);
                 else if (a.fuse_adam) adam_step(a.adam, j[b], g, xp[b], mp[b], vp[b]);
                 a.win[j[b]] = 0;  // scratch back to zero for the next call
             }
@@ -450,12 +480,18 @@ __global__ void __launch_bounds__(STG_WG) win_emit1t(Win1Args a) {
         for (uint32_t b = 0; b < WP; ++b) v[b] = a.m ? a.val[std::min<size_t>(e + b, a.m - 1)] : 0.f;
     }
     float xp[WP], mp[WP], vp[WP];
+    uint32_t lp[WP];
     if (a.fuse_sgd) {  // the winners' parameter and momentum words, loaded under the look-back
 #pragma unroll
         for (uint32_t b = 0; b < WP; ++b) {
             const uint32_t id = (keep >> b & 1u) ? j[b] : 0u;
             xp[b] = a.sgd.param[id];
             mp[b] = a.sgd.mom ? a.sgd.mom[id] : 0.f;
+            lp[b] = SMART ? a.sgd.last[id] : 0u;
+        }
+        if (SMART) {
+#pragma unroll
+            for (uint32_t b = 0; b < WP; ++b) vp[b] = sgd_factor<SMART>(a.sgd, lp[b]);
         }
     } else if (a.fuse_adam) {
 #pragma unroll
@@ -512,7 +548,8 @@ __global__ void __launch_bounds__(STG_WG) win_emit1t(Win1Args a) {
                 a.out_idx[P + r] = j[b];
                 a.out_val[P + r] = g;
             }
-            if (a.fuse_sgd) sgd_step(a.sgd, j[b], g, xp[b], mp[b]);  // each index elected once: updates commute
+            if (a.fuse_sgd)  // each index elected once: updates commute
+                sgd_step<SMART>(a.sgd, j[b], g, xp[b], mp[b], SMART ? vp[b] : a.sgd.momentum, lp[b]);
             else if (a.fuse_adam) adam_step(a.adam, j[b], g, xp[b], mp[b], vp[b]);
             a.win[j[b]] = 0;  // scratch back to zero for the next call
             ++r;
@@ -535,6 +572,11 @@ __device__ __forceinline__ uint32_t dev_len(uint32_t cap, const uint32_t *d_len)
     return c == POISON_COUNT ? 0u : min(cap, c);
 }
 
+// SMART: a caller's stream may repeat an index, so the last-touched word is
+// exchanged, not loaded: of two elements on one index exactly one finds the
+// word already at `iter` (the reference's assertion, sgd.cpp:229-232), is
+// skipped and flags the handle.
+template <bool SMART>
 __global__ void __launch_bounds__(STG_WG) sgd_apply(SgdLaunch a) {
     const uint32_t len = dev_len(a.grad_len, a.d_grad_len);
     const uint32_t stride = gridDim.x * STG_WG;
@@ -543,10 +585,20 @@ __global__ void __launch_bounds__(STG_WG) sgd_apply(SgdLaunch a) {
         if (id >= a.param_len) continue;  // an index past the parameter (bad input): never written
         const float x = a.param[id];
         float g = a.grad[i];
+        float f = a.momentum;
+        if (SMART) {
+            const uint32_t last = __hip_atomic_exchange(gp(a.last + id), a.iter, __ATOMIC_RELAXED,
+                                                        __HIP_MEMORY_SCOPE_AGENT);
+            if (a.iter != 0 && last == a.iter) {
+                g_or(a.fail, SGD_FAIL_FACTOR);
+                continue;
+            }
+            f = sgd_factor<true>(a, last);
+        }
         if (a.weight_decay != 0.f) g = fmaf(a.weight_decay, x, g);
         if (a.mom) {
-            const float b = a.first ? g : fmaf(a.mom[id], a.momentum, (1.0f - a.dampening) * g);
-            g = a.nesterov ? fmaf(a.momentum, b, g) : b;
+            const float b = a.first ? g : fmaf(a.mom[id], f, (1.0f - a.dampening) * g);
+            g = a.nesterov ? fmaf(f, b, g) : b;
             a.mom[id] = b;
         }
         a.param[id] = (float)fma(-a.lr, (double)g, (double)x);
@@ -776,7 +828,8 @@ hipError_t launch_scatter_merge(const uint32_t *idx, const float *val, size_t pe
             Win1Args a{idx, val, per_rank, n, nt1, win, w1.desc, w1.ticket, 0ull /* win_mark zeroed it */, w1.tag,
                        out_idx, out_val, out_count, w1.fail, w1.dup, w1.sgd != nullptr,
                        w1.sgd ? *w1.sgd : SgdLaunch{}, w1.adam != nullptr, w1.adam ? *w1.adam : AdamLaunch{}};
-            win_emit1t<wp><<<nt1, STG_WG, 0, s>>>(a);
+            if (a.fuse_sgd && a.sgd.last) win_emit1t<wp, true><<<nt1, STG_WG, 0, s>>>(a);
+            else win_emit1t<wp, false><<<nt1, STG_WG, 0, s>>>(a);
             if (w1.grid_out) *w1.grid_out = nt1;
             return hipGetLastError();
         }
@@ -810,7 +863,8 @@ hipError_t launch_scatter_merge(const uint32_t *idx, const float *val, size_t pe
 
 hipError_t launch_sgd(const SgdLaunch &a, hipStream_t s) {
     const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((a.grad_len + STG_WG - 1) / STG_WG, 2048));
-    sgd_apply<<<blocks, STG_WG, 0, s>>>(a);
+    if (a.last) sgd_apply<true><<<blocks, STG_WG, 0, s>>>(a);
+    else sgd_apply<false><<<blocks, STG_WG, 0, s>>>(a);
     return hipGetLastError();
 }
 

@@ -315,9 +315,18 @@ struct stg_sgd {
     uint32_t iter = 0;
     std::mutex mu;
     std::unordered_map<std::string, std::pair<float *, uint32_t>> mom;
+    // smart momentum (sgd.cpp:54, 225-232, 258-259)
+    bool smart = false;
+    std::unordered_map<std::string, std::pair<uint32_t *, uint32_t>> last;  // per name, zeroed when first needed
+    float *pow_tab = nullptr;  // pow(momentum, d), d < pow_len; built once (the momentum never changes), kept until destroy
+    uint32_t pow_len = 0;
+    uint32_t *fail = nullptr;  // device failure word (SGD_FAIL_FACTOR)
     ~stg_sgd() {
         (void)hipSetDevice(device);
         for (auto &kv : mom) (void)hipFree(kv.second.first);
+        for (auto &kv : last) (void)hipFree(kv.second.first);
+        (void)hipFree(pow_tab);
+        (void)hipFree(fail);
     }
 };
 
@@ -1121,8 +1130,23 @@ static int sgd_prepare(stg_sgd_t o, const char *name, float *d_param, uint32_t p
                        stg::SgdLaunch *out) {
     bool first = false;
     float *mom = nullptr;
+    uint32_t *last = nullptr;
+    uint32_t iter;
     {
         std::lock_guard<std::mutex> g(o->mu);
+        if (o->smart) {  // the reference's array is zero until the option is on (sgd.cpp:46-47, 258-259)
+            auto it = o->last.find(name);
+            if (it == o->last.end()) {
+                uint32_t *b = nullptr;
+                HIP_TRY(hipMalloc(&b, std::max<size_t>(param_len, 1) * sizeof(uint32_t)));
+                HIP_TRY(hipMemsetAsync(b, 0, std::max<size_t>(param_len, 1) * sizeof(uint32_t), s));
+                it = o->last.emplace(name, std::make_pair(b, param_len)).first;
+            }
+            if (it->second.second != param_len)
+                return fail(STG_ERR_INVALID, "param_len differs from the name's first smart-momentum call");
+            last = it->second.first;
+        }
+        iter = o->iter;
         if (o->momentum != 0.f) {
             auto it = o->mom.find(name);
             if (it == o->mom.end()) {  // sgd.cpp:40-47: zeroed buffer, first = true
@@ -1148,6 +1172,11 @@ static int sgd_prepare(stg_sgd_t o, const char *name, float *d_param, uint32_t p
     a.weight_decay = o->weight_decay;
     a.lr = o->maximize ? -(double)o->lr : (double)o->lr;  // sgd.cpp:51
     a.nesterov = o->nesterov;
+    a.last = last;
+    a.iter = iter;
+    a.pow_tab = o->pow_tab;
+    a.pow_len = o->pow_len;
+    a.fail = o->fail;
     *out = a;
     return STG_OK;
 }
@@ -1218,6 +1247,94 @@ int stg_sgd_get_momentum(stg_sgd_t o, const char *name, float *host_out, uint32_
     }
     HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     HIP_TRY(hipMemcpy(host_out, b, std::min(len, n) * sizeof(float), hipMemcpyDeviceToHost));
+    return STG_OK;
+}
+
+// The factor table of smart momentum: (float)pow((double)m, (double)d) by the
+// host's libm, as sgd.cpp:226 computes it, for d = 0 .. d0, d0 the first d that
+// gives 0.f (m < 1: the values fall monotonically, so every later one is 0 too).
+constexpr size_t SGD_POW_CAP = size_t(1) << 22;  // entries; m = 0.9999 needs ~1.04 M
+
+int stg_sgd_set_smart_momentum(stg_sgd_t o, int on) {
+    if (!o) return fail(STG_ERR_INVALID, "null argument");
+    if (!on) {
+        std::lock_guard<std::mutex> g(o->mu);
+        o->smart = false;
+        return STG_OK;
+    }
+    // momentum 0: the reference has no last-touched array to read (sgd.cpp:43-54);
+    // outside (0, 1) every factor trips its range assertion (sgd.cpp:229-232)
+    if (!(o->momentum > 0.f && o->momentum < 1.f))
+        return fail(STG_ERR_INVALID, "smart momentum needs 0 < momentum < 1");
+    std::lock_guard<std::mutex> g(o->mu);
+    if (!o->pow_tab) {
+        std::vector<float> tab;
+        for (;;) {
+            const float v = (float)std::pow((double)o->momentum, (double)tab.size());
+            tab.push_back(v);
+            if (v == 0.f) break;
+            if (tab.size() >= SGD_POW_CAP)
+                return fail(STG_ERR_UNSUPPORTED, "smart momentum: the factor table of this momentum exceeds 2^22 entries");
+        }
+        HIP_TRY(hipSetDevice(o->device));
+        float *t = nullptr;
+        uint32_t *f = nullptr;
+        HIP_TRY(hipMalloc(&t, tab.size() * sizeof(float)));
+        if (hipMemcpy(t, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMalloc(&f, sizeof(uint32_t)) != hipSuccess || hipMemset(f, 0, sizeof(uint32_t)) != hipSuccess ||
+            hipDeviceSynchronize() != hipSuccess) {
+            (void)hipFree(t);
+            (void)hipFree(f);
+            return fail(STG_ERR_HIP, "smart momentum: uploading the factor table failed");
+        }
+        // resident before any launch can name it; never moved or freed before destroy
+        o->pow_tab = t;
+        o->pow_len = (uint32_t)tab.size();
+        o->fail = f;
+    }
+    o->smart = true;
+    return STG_OK;
+}
+
+int stg_sgd_get_last(stg_sgd_t o, const char *name, uint32_t *host_out, uint32_t len, void *stream) {
+    if (!o || !name || (len && !host_out)) return fail(STG_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(o->device));
+    uint32_t *b = nullptr;
+    uint32_t n = 0;
+    {
+        std::lock_guard<std::mutex> g(o->mu);
+        auto it = o->last.find(name);
+        if (it == o->last.end()) return fail(STG_ERR_INVALID, "no smart-momentum state for this name");
+        b = it->second.first;
+        n = it->second.second;
+    }
+    HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    HIP_TRY(hipMemcpy(host_out, b, std::min(len, n) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return STG_OK;
+}
+
+int stg_sgd_get_iter(stg_sgd_t o, uint32_t *out) {
+    if (!o || !out) return fail(STG_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> g(o->mu);
+    *out = o->iter;
+    return STG_OK;
+}
+
+int stg_sgd_check(stg_sgd_t o, void *stream) {
+    if (!o) return fail(STG_ERR_INVALID, "null argument");
+    uint32_t *fw = nullptr;
+    {
+        std::lock_guard<std::mutex> g(o->mu);
+        fw = o->fail;
+    }
+    if (!fw) return STG_OK;  // the option was never on: nothing can have failed
+    HIP_TRY(hipSetDevice(o->device));
+    HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    uint32_t f = 0;
+    HIP_TRY(hipMemcpy(&f, fw, sizeof f, hipMemcpyDeviceToHost));
+    if (f)
+        return fail(STG_ERR_DEVICE, "sgd: a smart-momentum factor was outside [0, 1) (an index repeated within one "
+                                    "call); those elements were skipped");
     return STG_OK;
 }
 

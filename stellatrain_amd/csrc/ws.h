@@ -385,7 +385,15 @@ struct SgdLaunch {
     float momentum, dampening, weight_decay;
     double lr;
     bool nesterov;
+    // smart momentum (sgd.cpp:225-227, 258-259): the factor is
+    // pow(momentum, iter - last[id]) in place of momentum
+    uint32_t *last;        // per name: the iteration that last touched each index (param_len words); null: option off
+    uint32_t iter;         // the optimizer's call count before this call (shared by all names)
+    const float *pow_tab;  // pow_tab[d] = (float)pow((double)momentum, (double)d), filled by the host's libm
+    uint32_t pow_len;      // its entries; the last one is 0.f and so is every factor past it
+    uint32_t *fail;        // sticky failure word of the optimizer handle (SGD_FAIL_FACTOR)
 };
+constexpr uint32_t SGD_FAIL_FACTOR = 1u;  // a factor outside [0, 1): an index repeated within one call
 hipError_t launch_sgd(const SgdLaunch &a, hipStream_t s);
 
 struct AdamLaunch {

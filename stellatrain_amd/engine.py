@@ -296,15 +296,50 @@ def _merge_optimize(fn, h, param, name, idx, val, per_rank, world, dense, mark, 
 
 class SparseSGD:
     """``SGD`` sparse optimizer (optim/sgd.h:10-50) on the device.  Options as
-    SGD::configure (sgd.cpp:265-300); ``optimize_raw`` as sgd.cpp:34-263."""
+    SGD::configure (sgd.cpp:265-300); ``optimize_raw`` as sgd.cpp:34-263.
+
+    ``smart_momentum`` (sgd.cpp:291-292): a touched element's buffer decays by
+    ``momentum ** (iterations since its index was last touched)``.  The
+    iteration count is the optimizer's, shared by all names."""
 
     def __init__(self, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
-                 nesterov: bool = False, maximize: bool = False, device: int = 0):
+                 nesterov: bool = False, maximize: bool = False, device: int = 0, smart_momentum: bool = False):
         h = C.c_void_p()
         check(lib().stg_sgd_create(device, lr, momentum, dampening, weight_decay, int(nesterov), int(maximize),
                                    C.byref(h)))
         self._h = h
         self.device = device
+        if smart_momentum:
+            self.configure("smart_momentum", True)
+
+    def configure(self, option_name: str, option_value) -> None:
+        """SGD::configure(name, bool) for the option set after construction
+        (sgd.cpp:284-297); any other name raises as the reference throws."""
+        if option_name != "smart_momentum" or not isinstance(option_value, (bool, np.bool_)):
+            raise CodecError(-1, "NO OPTION")
+        check(lib().stg_sgd_set_smart_momentum(self._h, int(option_value)))
+
+    @property
+    def iteration(self) -> int:
+        """Calls made so far on this optimizer, over all names (m_iter)."""
+        it = C.c_uint32()
+        check(lib().stg_sgd_get_iter(self._h, C.byref(it)))
+        return int(it.value)
+
+    def check(self) -> None:
+        """Raise CodecError (STG_ERR_DEVICE) if a smart-momentum element was
+        ever skipped: an index repeated within one call.  Syncs the stream."""
+        import torch
+        check(lib().stg_sgd_check(self._h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+
+    def last_buffer(self, name: str, n: int):
+        """The iteration that last touched each index of ``name`` (uint32), or
+        None before the name's first call with smart momentum on."""
+        import torch
+        out = np.zeros(n, np.uint32)
+        rc = lib().stg_sgd_get_last(self._h, name.encode(), C.c_void_p(out.ctypes.data), n,
+                                    C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        return None if rc else out
 
     def __del__(self):
         h = getattr(self, "_h", None)

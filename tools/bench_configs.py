@@ -246,6 +246,8 @@ def make_opt(kind):
     from stellatrain_amd import SparseAdam, SparseSGD
     if kind == "sgd":
         return SparseSGD(lr=0.1, momentum=0.9), "SGD(m=0.9)"
+    if kind == "sgd_smart":  # sgd.cpp:291-292; nine names on one counter: every gap is 9 iterations
+        return SparseSGD(lr=0.1, momentum=0.9, smart_momentum=True), "SGD(m=0.9, smart momentum)"
     if kind == "adam":
         return SparseAdam(lr=1e-3), "Adam"
     return SparseAdam(lr=1e-3, amsgrad=True), "Adam(amsgrad)"
@@ -296,6 +298,8 @@ def c5_round_trip(torch, steps, kind="sgd"):
     torch.cuda.synchronize()
     us = e0.elapsed_time(e1) * 1e3 / steps
     alg = 4.0 * n + 8.0 * k + (24.0 if kind.startswith("adam") else 16.0) * k
+    if kind.startswith("sgd_smart"):
+        alg += 8.0 * k  # the last-touched word, read and written (the factor table stays in L2)
     return {"config": f"C5 thresholdv16 compress + decompress + {label} 64 MiB k={k}", "us_per_step": round(us, 2),
             "host_enqueue_us_per_step": round(host_us, 2),
             "GBps_dense_in": round(4.0 * n / us / 1e3, 1), "alg_GBps": round(alg / us / 1e3, 1)}
@@ -650,8 +654,9 @@ def main():
         emit(host_inclusive(torch, "thresholdv16", 64, 0.99, 24))
     if "single" in only:  # one 64 MiB bucket per call, one stream: the latency of a lone call
         emit(time_device(torch, make_compressor("thresholdv16"), "thresholdv16 single-bucket", 64, 0.99, a.calls, 8, 16))
-    if "c5" in only:
-        for kind in ("sgd", "sgd_fused", "adam", "adam_fused", "adam_ams"):
+    if "c5" in only or "c5sgd" in only:  # "c5sgd": the SGD rows alone
+        sgd_kinds = ("sgd", "sgd_smart", "sgd_fused", "sgd_smart_fused")
+        for kind in sgd_kinds + (("adam", "adam_fused", "adam_ams") if "c5" in only else ()):
             emit(c5_round_trip(torch, a.calls, kind))
     if "gfused" in only:
         for r in gather_fused(torch, a.calls):
