@@ -322,6 +322,62 @@ typedef struct stg_wire_stream {
  * launches of up to 16 streams instead of one launch per stream. */
 int stg_wire_encode_batch_device(const stg_wire_stream_t *streams, size_t nstreams, void *stream);
 
+/* One received stream of a batched decode: the arguments of one decode call. */
+typedef struct stg_wire_rx {
+    const void *d_idx_in;
+    const void *d_val_in;
+    size_t numel;
+    int flag;
+    uint32_t *d_idx;
+    float *d_val;
+} stg_wire_rx_t;
+
+/* Batched stg_wire_decode_device: the same bytes as decoding streams[0..n-1]
+ * one by one, in launches of up to 16 streams (for consumers that want the
+ * decoded pairs; the MERGE calls below read the wire form themselves). */
+int stg_wire_decode_batch_device(const stg_wire_rx_t *streams, size_t nstreams, void *stream);
+
+/* One rank's received stream of a MERGE decompress, where it landed and in
+ * the form it arrived in: per_rank u16 (flag & STG_WIRE_U16_IDX) or u32
+ * indices, per_rank fp16 bits (flag & STG_WIRE_F16_VAL) or floats; flag as
+ * stg_wire_flag returns it. */
+typedef struct stg_rank_stream {
+    const void *d_idx;
+    const void *d_val;
+    int flag;
+} stg_rank_stream_t;
+
+/* The MERGE decompress and the fused optimizer steps straight from received
+ * streams (the receiver's decode, comm_manager.cpp:877-906, inside the merge's
+ * own loads).  The results -- the merged stream and its count, parameters,
+ * optimizer state, iteration count -- are bitwise those of
+ * stg_wire_decode_device(per_rank, ranks[r].flag) of every rank into position
+ * r * per_rank of one u32 / f32 buffer followed by the decoded entry point
+ * (stg_scatter_merge_device, stg_merge_optimize_{sgd,adam}_device), without
+ * the `world` decode launches and that buffer.  The decode is by position:
+ * pair i < 8 * ((per_rank - 1) / 8) sign-extends its u16 index (one >= 0x8000
+ * becomes >= n and is dropped) and widens its fp16 value; the last 1..8 pairs
+ * zero-extend and take (float) of the 16-bit integer.  `ranks` is a host array
+ * of `world` entries read at call time; the buffers need not be adjacent, and
+ * a 16-bit buffer needs only 2-byte alignment (8-byte aligned ones are read
+ * four pairs per load) and is never read past pair per_rank - 1.  With every
+ * flag 0 this is the decoded call over separate buffers.  Scratch, failure
+ * word, check and release are those of stg_scatter_merge_device.
+ * STG_ERR_INVALID before any device call: world < 1, null `ranks` or a null
+ * buffer with per_rank > 0, a flag outside 0..3, missing or misaligned
+ * d_dense / d_mark at world > 1. */
+int stg_scatter_merge_wire_device(const stg_rank_stream_t *ranks, size_t per_rank, int world, size_t n,
+                                  float *d_dense, uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
+                                  uint32_t *d_out_count, void *stream);
+int stg_merge_optimize_sgd_wire_device(stg_sgd_t o, const char *name, float *d_param, uint32_t param_len,
+                                       const stg_rank_stream_t *ranks, size_t per_rank, int world, float *d_dense,
+                                       uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
+                                       uint32_t *d_out_count, void *stream);
+int stg_merge_optimize_adam_wire_device(stg_adam_t o, const char *name, float *d_param, uint32_t param_len,
+                                        const stg_rank_stream_t *ranks, size_t per_rank, int world, float *d_dense,
+                                        uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
+                                        uint32_t *d_out_count, void *stream);
+
 /* Synthetic fp32 buckets from the integer-only generator of SURVEY 8(d)
  * (dist 0 = D1, 1 = D2 heavy tail, 2 = D3 zeros with prob param/1e4);
  * bit-identical to oracle/stg_oracle.cpp:orc_synth_fill. */

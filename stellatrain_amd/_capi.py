@@ -35,6 +35,17 @@ class StgBucket(C.Structure):
                 ("idx_offset", C.c_int32), ("d_count", C.c_void_p)]
 
 
+class StgRankStream(C.Structure):
+    """``stg_rank_stream_t``: one rank's received stream of a MERGE decompress."""
+    _fields_ = [("d_idx", C.c_void_p), ("d_val", C.c_void_p), ("flag", C.c_int)]
+
+
+class StgWireRx(C.Structure):
+    """``stg_wire_rx_t``: one received stream of a batched decode."""
+    _fields_ = [("d_idx_in", C.c_void_p), ("d_val_in", C.c_void_p), ("numel", C.c_size_t), ("flag", C.c_int),
+                ("d_idx", C.c_void_p), ("d_val", C.c_void_p)]
+
+
 _lib: C.CDLL | None = None
 
 _SIGS = {
@@ -95,6 +106,15 @@ _SIGS = {
     "stg_wire_decode_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
     "stg_wire_encode_batch_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "stg_wire_decode_batch_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "stg_scatter_merge_wire_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "stg_merge_optimize_sgd_wire_device": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                     C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "stg_merge_optimize_adam_wire_device": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                      C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "stg_synth_fill_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_int, C.c_uint32, C.c_void_p]),
     "stg_last_error": (C.c_char_p, []),
 }

@@ -44,8 +44,10 @@
 //   elements are independent apart from vmax.
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "ws.h"
+#include "wire_dev.h"
 
 namespace stg {
 
@@ -58,12 +60,19 @@ constexpr uint32_t MARK_TILE = MERGE_TILE;  // marks (or pairs) per tile (one ui
 // With `dup` (world 1): any repeated or out-of-range index sets it (the
 // emission then elects; otherwise every pair is its index's only occurrence and
 // the emission copies the stream), and the emission's tile ticket starts at 0.
-__global__ void __launch_bounds__(STG_WG) win_mark(const uint32_t *__restrict__ idx, size_t m, size_t n,
-                                                   uint32_t *__restrict__ win, uint32_t *dup, uint64_t *ticket) {
+//
+// WIRE (here and below): the stream is read in the form it arrived in, `flag`
+// (STG_WIRE_* bits) and `wend` = 8 * ((m - 1) / 8) given -- the pair decoded as
+// wire_decode would (wire_dev.h).  The decoded kernels are the WIRE = false
+// bodies under their own names and arguments.
+template <bool WIRE>
+__device__ __forceinline__ void win_mark_body(const uint32_t *__restrict__ idx, size_t m, size_t n,
+                                              uint32_t *__restrict__ win, uint32_t *dup, uint64_t *ticket,
+                                              uint32_t flag, size_t wend) {
     if (ticket && blockIdx.x == 0 && threadIdx.x == 0) st_sc1(ticket, 0ull);
     const size_t stride = (size_t)gridDim.x * STG_WG;
     for (size_t i = (size_t)blockIdx.x * STG_WG + threadIdx.x; i < m; i += stride) {
-        const uint32_t j = idx[i];
+        const uint32_t j = WIRE ? wire_get_idx(idx, flag, wend, i) : idx[i];
         if (!dup) {
             if (j < n) atomicMax(&win[j], (uint32_t)i + 1u);
         } else if (j >= n || atomicMax(&win[j], (uint32_t)i + 1u) != 0u) {
@@ -71,17 +80,15 @@ __global__ void __launch_bounds__(STG_WG) win_mark(const uint32_t *__restrict__ 
         }
     }
 }
-
-// world == 1, pass 1: winners per tile of MARK_TILE pairs.
-__global__ void __launch_bounds__(STG_WG) win_count(const uint32_t *__restrict__ idx, size_t m, size_t n,
-                                                    const uint32_t *__restrict__ win, uint32_t *__restrict__ tile_cnt);
-// world == 1, pass 2: ordered compaction of the winners (look-up of the
-// earlier tiles' counts), re-zeroing their scratch words.
-__global__ void __launch_bounds__(STG_WG) win_emit1(const uint32_t *__restrict__ idx, const float *__restrict__ val,
-                                                    size_t m, size_t n, uint32_t ntiles, uint32_t *__restrict__ win,
-                                                    const uint32_t *__restrict__ tile_cnt,
-                                                    uint32_t *__restrict__ out_idx, float *__restrict__ out_val,
-                                                    uint32_t *out_count);
+__global__ void __launch_bounds__(STG_WG) win_mark(const uint32_t *__restrict__ idx, size_t m, size_t n,
+                                                   uint32_t *__restrict__ win, uint32_t *dup, uint64_t *ticket) {
+    win_mark_body<false>(idx, m, n, win, dup, ticket, 0u, 0);
+}
+__global__ void __launch_bounds__(STG_WG) win_mark_w(const void *__restrict__ idx, size_t m, size_t n,
+                                                     uint32_t *__restrict__ win, uint32_t *dup, uint64_t *ticket,
+                                                     uint32_t flag, size_t wend) {
+    win_mark_body<true>(static_cast<const uint32_t *>(idx), m, n, win, dup, ticket, flag, wend);
+}
 
 // world > 1: rank r's scatter and rank r+1's winner election in one launch,
 // on the two halves of the election scratch (rank parity), so a rank's
@@ -104,6 +111,30 @@ __global__ void __launch_bounds__(STG_WG) scatter_mark(const uint32_t *__restric
             if (!midx) continue;
             const size_t i = t - m;
             const uint32_t j = midx[i];
+            if (j < n) atomicMax(&mwin[j], (uint32_t)i + 1u);
+        }
+    }
+}
+// The same on received streams: the scattered and the elected rank each with
+// its own pointers and flag (both hold m pairs, so they share wend).
+__global__ void __launch_bounds__(STG_WG) scatter_mark_w(const void *__restrict__ sidx, const void *__restrict__ sval,
+                                                         uint32_t sflag, uint32_t *__restrict__ swin,
+                                                         const void *__restrict__ midx, uint32_t mflag,
+                                                         uint32_t *__restrict__ mwin, size_t m, size_t n, size_t wend,
+                                                         float *__restrict__ dense, uint8_t *__restrict__ mark) {
+    const size_t stride = (size_t)gridDim.x * STG_WG;
+    for (size_t t = (size_t)blockIdx.x * STG_WG + threadIdx.x; t < 2 * m; t += stride) {
+        if (t < m) {
+            if (!sidx) continue;
+            const uint32_t j = wire_get_idx(sidx, sflag, wend, t);
+            if (j >= n || swin[j] != (uint32_t)t + 1u) continue;  // a later occurrence wins
+            swin[j] = 0;
+            dense[j] += wire_get_val(sval, sflag, wend, t);
+            mark[j] = 1;
+        } else {
+            if (!midx) continue;
+            const size_t i = t - m;
+            const uint32_t j = wire_get_idx(midx, mflag, wend, i);
             if (j < n) atomicMax(&mwin[j], (uint32_t)i + 1u);
         }
     }
@@ -213,14 +244,35 @@ __global__ void __launch_bounds__(STG_WG) mark_emit_tile(uint8_t *__restrict__ m
 constexpr uint32_t WPER = MARK_TILE / STG_WG;  // 16 consecutive pairs per lane
 static_assert(WPER == 16, "four uint4 of indices per lane");
 
+// WIRE: the lane's WP pairs (e % 4 == 0, WP % 4 == 0) of a received stream,
+// four at a time (wire_dev.h: an 8-byte load of the 16-bit form where the four
+// exist and are aligned, clamped single loads otherwise).
+template <uint32_t WP>
+__device__ __forceinline__ void wire_idx_wp(const void *idx, uint32_t flag, size_t wend, size_t m, size_t e,
+                                            uint32_t (&j)[WP]) {
+    static_assert(WP % 4 == 0, "groups of four pairs");
+#pragma unroll
+    for (uint32_t q = 0; q < WP / 4; ++q) wire_get_idx4(idx, flag, wend, m, e + 4 * q, &j[4 * q]);
+}
+template <uint32_t WP>
+__device__ __forceinline__ void wire_val_wp(const void *val, uint32_t flag, size_t wend, size_t m, size_t e,
+                                            float (&v)[WP]) {
+    static_assert(WP % 4 == 0, "groups of four pairs");
+#pragma unroll
+    for (uint32_t q = 0; q < WP / 4; ++q) wire_get_val4(val, flag, wend, m, e + 4 * q, &v[4 * q]);
+}
+
 // The lane's 16 pairs e .. e+15: their indices, and which of them win (bit b).
 // Every load is issued before any is used -- the 16 index loads together,
 // then the 16 winner words (clamped addresses, results masked) -- two round
 // trips per lane instead of 32 dependent ones.
-template <uint32_t WP>
+template <uint32_t WP, bool WIRE = false>
 __device__ __forceinline__ uint32_t win_keep_t(const uint32_t *__restrict__ idx, size_t m, size_t n,
-                                               const uint32_t *__restrict__ win, size_t e, uint32_t (&j)[WP]) {
-    if (WP % 4 == 0 && e + WP <= m && (reinterpret_cast<uintptr_t>(idx + e) & 15u) == 0) {
+                                               const uint32_t *__restrict__ win, size_t e, uint32_t (&j)[WP],
+                                               uint32_t flag = 0, size_t wend = 0) {
+    if (WIRE) {
+        wire_idx_wp<WP>(idx, flag, wend, m, e, j);
+    } else if (WP % 4 == 0 && e + WP <= m && (reinterpret_cast<uintptr_t>(idx + e) & 15u) == 0) {
         const uint4 *p = reinterpret_cast<const uint4 *>(idx + e);
 #pragma unroll
         for (uint32_t q = 0; q < WP / 4; ++q) {
@@ -240,17 +292,22 @@ __device__ __forceinline__ uint32_t win_keep_t(const uint32_t *__restrict__ idx,
         if (e + b < m && j[b] < n && w[b] == (uint32_t)(e + b) + 1u) keep |= 1u << b;
     return keep;
 }
+template <bool WIRE>
 __device__ __forceinline__ uint32_t win_keep(const uint32_t *__restrict__ idx, size_t m, size_t n,
-                                             const uint32_t *__restrict__ win, size_t e, uint32_t (&j)[WPER]) {
-    return win_keep_t<WPER>(idx, m, n, win, e, j);
+                                             const uint32_t *__restrict__ win, size_t e, uint32_t (&j)[WPER],
+                                             uint32_t flag, size_t wend) {
+    return win_keep_t<WPER, WIRE>(idx, m, n, win, e, j, flag, wend);
 }
 
-__global__ void __launch_bounds__(STG_WG) win_count(const uint32_t *__restrict__ idx, size_t m, size_t n,
-                                                    const uint32_t *__restrict__ win, uint32_t *__restrict__ tile_cnt) {
+// world == 1, pass 1: winners per tile of MARK_TILE pairs.
+template <bool WIRE>
+__device__ __forceinline__ void win_count_body(const uint32_t *__restrict__ idx, size_t m, size_t n,
+                                               const uint32_t *__restrict__ win, uint32_t *__restrict__ tile_cnt,
+                                               uint32_t flag, size_t wend) {
     __shared__ uint32_t s[STG_WAVES];
     const size_t e = (size_t)blockIdx.x * MARK_TILE + (size_t)WPER * threadIdx.x;
     uint32_t j[WPER];
-    uint32_t c = e < m ? (uint32_t)__popc(win_keep(idx, m, n, win, e, j)) : 0u;
+    uint32_t c = e < m ? (uint32_t)__popc(win_keep<WIRE>(idx, m, n, win, e, j, flag, wend)) : 0u;
     c = wave_sum(c);
     if (__lane_id() == 0) s[threadIdx.x >> 6] = c;
     __syncthreads();
@@ -260,12 +317,24 @@ __global__ void __launch_bounds__(STG_WG) win_count(const uint32_t *__restrict__
         tile_cnt[blockIdx.x] = t;
     }
 }
+__global__ void __launch_bounds__(STG_WG) win_count(const uint32_t *__restrict__ idx, size_t m, size_t n,
+                                                    const uint32_t *__restrict__ win, uint32_t *__restrict__ tile_cnt) {
+    win_count_body<false>(idx, m, n, win, tile_cnt, 0u, 0);
+}
+__global__ void __launch_bounds__(STG_WG) win_count_w(const void *__restrict__ idx, size_t m, size_t n,
+                                                      const uint32_t *__restrict__ win,
+                                                      uint32_t *__restrict__ tile_cnt, uint32_t flag, size_t wend) {
+    win_count_body<true>(static_cast<const uint32_t *>(idx), m, n, win, tile_cnt, flag, wend);
+}
 
-__global__ void __launch_bounds__(STG_WG) win_emit1(const uint32_t *__restrict__ idx, const float *__restrict__ val,
-                                                    size_t m, size_t n, uint32_t ntiles, uint32_t *__restrict__ win,
-                                                    const uint32_t *__restrict__ tile_cnt,
-                                                    uint32_t *__restrict__ out_idx, float *__restrict__ out_val,
-                                                    uint32_t *out_count) {
+// world == 1, pass 2: ordered compaction of the winners (look-up of the
+// earlier tiles' counts), re-zeroing their scratch words.
+template <bool WIRE>
+__device__ __forceinline__ void win_emit1_body(const uint32_t *__restrict__ idx, const float *__restrict__ val,
+                                               size_t m, size_t n, uint32_t ntiles, uint32_t *__restrict__ win,
+                                               const uint32_t *__restrict__ tile_cnt, uint32_t *__restrict__ out_idx,
+                                               float *__restrict__ out_val, uint32_t *out_count, uint32_t flag,
+                                               size_t wend) {
     __shared__ uint64_t sh64[STG_WAVES];
     __shared__ uint32_t sh[STG_WAVES + 1];
     const uint32_t G = gridDim.x, w = blockIdx.x, tid = threadIdx.x;
@@ -282,9 +351,11 @@ __global__ void __launch_bounds__(STG_WG) win_emit1(const uint32_t *__restrict__
     for (uint32_t tile = t_begin; tile < t_end; ++tile) {
         const size_t e = (size_t)tile * MARK_TILE + (size_t)WPER * tid;
         uint32_t j[WPER];
-        const uint32_t keep = e < m ? win_keep(idx, m, n, win, e, j) : 0u;
+        const uint32_t keep = e < m ? win_keep<WIRE>(idx, m, n, win, e, j, flag, wend) : 0u;
         float v[WPER];  // the values, loaded alongside (clamped addresses)
-        if (e + WPER <= m && (reinterpret_cast<uintptr_t>(val + e) & 15u) == 0) {
+        if (WIRE) {
+            if (e < m) wire_val_wp<WPER>(val, flag, wend, m, e, v);
+        } else if (e + WPER <= m && (reinterpret_cast<uintptr_t>(val + e) & 15u) == 0) {
             const float4 *p = reinterpret_cast<const float4 *>(val + e);
 #pragma unroll
             for (uint32_t q = 0; q < 4; ++q) {
@@ -309,6 +380,21 @@ __global__ void __launch_bounds__(STG_WG) win_emit1(const uint32_t *__restrict__
         P += tc;
     }
     if (w == 0 && tid == 0) *out_count = (uint32_t)total;
+}
+__global__ void __launch_bounds__(STG_WG) win_emit1(const uint32_t *__restrict__ idx, const float *__restrict__ val,
+                                                    size_t m, size_t n, uint32_t ntiles, uint32_t *__restrict__ win,
+                                                    const uint32_t *__restrict__ tile_cnt,
+                                                    uint32_t *__restrict__ out_idx, float *__restrict__ out_val,
+                                                    uint32_t *out_count) {
+    win_emit1_body<false>(idx, val, m, n, ntiles, win, tile_cnt, out_idx, out_val, out_count, 0u, 0);
+}
+__global__ void __launch_bounds__(STG_WG) win_emit1_w(const void *__restrict__ idx, const void *__restrict__ val,
+                                                      size_t m, size_t n, uint32_t ntiles, uint32_t *__restrict__ win,
+                                                      const uint32_t *__restrict__ tile_cnt,
+                                                      uint32_t *__restrict__ out_idx, float *__restrict__ out_val,
+                                                      uint32_t *out_count, uint32_t flag, size_t wend) {
+    win_emit1_body<true>(static_cast<const uint32_t *>(idx), static_cast<const float *>(val), m, n, ntiles, win,
+                         tile_cnt, out_idx, out_val, out_count, flag, wend);
 }
 
 // world == 1 in one launch after win_mark: tiles in ticket order (a workgroup
@@ -388,8 +474,13 @@ struct Win1Args {
 // workgroups and the gathers of 16) or 16 (4,096-pair tiles: 41 workgroups at
 // 167,772 pairs, 13 us per call in the C5 kernel trace).
 // SMART: the fused SGD step with smart momentum (a.sgd.last set).
-template <uint32_t WP, bool SMART>
-__global__ void __launch_bounds__(STG_WG) win_emit1t(Win1Args a) {
+// WIRE: a.idx / a.val point at the received stream, typed by a.wflag.
+struct Win1ArgsW : Win1Args {
+    uint32_t wflag;
+    size_t wend;
+};
+template <uint32_t WP, bool SMART, bool WIRE = false>
+__global__ void __launch_bounds__(STG_WG) win_emit1t(std::conditional_t<WIRE, Win1ArgsW, Win1Args> a) {
     __shared__ uint32_t sh[STG_WAVES + 1];
     __shared__ uint32_t s_tile, s_bad;
     __shared__ uint64_t s_P, s_psum[STG_WAVES];
@@ -403,8 +494,13 @@ __global__ void __launch_bounds__(STG_WG) win_emit1t(Win1Args a) {
         const size_t e = (size_t)blockIdx.x * (WP * STG_WG) + (size_t)WP * tid;
         uint32_t j[WP];
         float v[WP];
-        if (WP % 4 == 0 && e + WP <= a.m && (reinterpret_cast<uintptr_t>(a.idx + e) & 15u) == 0 &&
-            (reinterpret_cast<uintptr_t>(a.val + e) & 15u) == 0) {
+        if constexpr (WIRE) {
+            if (e < a.m) {
+                wire_idx_wp<WP>(a.idx, a.wflag, a.wend, a.m, e, j);
+                wire_val_wp<WP>(a.val, a.wflag, a.wend, a.m, e, v);
+            }
+        } else if (WP % 4 == 0 && e + WP <= a.m && (reinterpret_cast<uintptr_t>(a.idx + e) & 15u) == 0 &&
+                   (reinterpret_cast<uintptr_t>(a.val + e) & 15u) == 0) {
 #pragma unroll
             for (uint32_t q = 0; q < WP / 4; ++q) {
                 const uint4 x = reinterpret_cast<const uint4 *>(a.idx + e)[q];
@@ -466,9 +562,13 @@ __global__ void __launch_bounds__(STG_WG) win_emit1t(Win1Args a) {
     const uint32_t tile = s_tile;
     const size_t e = (size_t)tile * (WP * STG_WG) + (size_t)WP * tid;
     uint32_t j[WP];
-    const uint32_t keep = e < a.m ? win_keep_t<WP>(a.idx, a.m, a.n, a.win, e, j) : 0u;
+    uint32_t keep = 0;
+    if constexpr (WIRE) keep = e < a.m ? win_keep_t<WP, true>(a.idx, a.m, a.n, a.win, e, j, a.wflag, a.wend) : 0u;
+    else keep = e < a.m ? win_keep_t<WP>(a.idx, a.m, a.n, a.win, e, j) : 0u;
     float v[WP];
-    if (WP % 4 == 0 && e + WP <= a.m && (reinterpret_cast<uintptr_t>(a.val + e) & 15u) == 0) {
+    if constexpr (WIRE) {
+        if (e < a.m) wire_val_wp<WP>(a.val, a.wflag, a.wend, a.m, e, v);
+    } else if (WP % 4 == 0 && e + WP <= a.m && (reinterpret_cast<uintptr_t>(a.val + e) & 15u) == 0) {
         const float4 *p = reinterpret_cast<const float4 *>(a.val + e);
 #pragma unroll
         for (uint32_t q = 0; q < WP / 4; ++q) {
@@ -811,6 +911,19 @@ hipError_t launch_error_feedback(float *grad, size_t n, const uint32_t *idx, siz
     return hipGetLastError();
 }
 
+// world > 1, after the ranks' scatters: the marked indices in order.
+static hipError_t launch_mark_emit(size_t n, int world, float *dense, uint8_t *mark, uint32_t *out_idx,
+                                   float *out_val, uint32_t *out_count, uint32_t *scratch_tiles, hipStream_t s) {
+    const uint32_t ntiles = (uint32_t)((n + MARK_TILE - 1) / MARK_TILE);
+    if (!ntiles) return hipMemsetAsync(out_count, 0, sizeof(uint32_t), s);
+    // per-tile counts, their scan, then one workgroup per tile (the old
+    // mark_emit walked its tiles one after another: ~90 us at 64 MiB)
+    mark_count<<<ntiles, STG_WG, 0, s>>>(mark, n, scratch_tiles);
+    mark_scan<<<1, 1024, 0, s>>>(scratch_tiles, ntiles, out_count);
+    mark_emit_tile<<<ntiles, STG_WG, 0, s>>>(mark, dense, n, ntiles, (float)world, scratch_tiles, out_idx, out_val);
+    return hipGetLastError();
+}
+
 hipError_t launch_scatter_merge(const uint32_t *idx, const float *val, size_t per_rank, int world, size_t n,
                                 float *dense, uint8_t *mark, uint32_t *out_idx, float *out_val,
                                 uint32_t *out_count, uint32_t *scratch_tiles, uint32_t *win, int num_cu,
@@ -851,14 +964,63 @@ hipError_t launch_scatter_merge(const uint32_t *idx, const float *val, size_t pe
                                                win + (size_t)(r & 1) * n, per_rank, n, dense, mark);
         }
     }
-    const uint32_t ntiles = (uint32_t)((n + MARK_TILE - 1) / MARK_TILE);
-    if (!ntiles) return hipMemsetAsync(out_count, 0, sizeof(uint32_t), s);
-    // per-tile counts, their scan, then one workgroup per tile (the old
-    // mark_emit walked its tiles one after another: ~90 us at 64 MiB)
-    mark_count<<<ntiles, STG_WG, 0, s>>>(mark, n, scratch_tiles);
-    mark_scan<<<1, 1024, 0, s>>>(scratch_tiles, ntiles, out_count);
-    mark_emit_tile<<<ntiles, STG_WG, 0, s>>>(mark, dense, n, ntiles, (float)world, scratch_tiles, out_idx, out_val);
-    return hipGetLastError();
+    return launch_mark_emit(n, world, dense, mark, out_idx, out_val, out_count, scratch_tiles, s);
+}
+
+hipError_t launch_scatter_merge_wire(const RankStream *ranks, size_t per_rank, int world, size_t n, float *dense,
+                                     uint8_t *mark, uint32_t *out_idx, float *out_val, uint32_t *out_count,
+                                     uint32_t *scratch_tiles, uint32_t *win, int num_cu, hipStream_t s,
+                                     const Win1Desc &w1) {
+    const size_t wend = per_rank ? 8 * ((per_rank - 1) / 8) : 0;
+    if (world == 1) {
+        const RankStream &k = ranks[0];
+        if (!k.flag)  // already u32 / f32: today's kernels
+            return launch_scatter_merge(static_cast<const uint32_t *>(k.idx), static_cast<const float *>(k.val),
+                                        per_rank, 1, n, dense, mark, out_idx, out_val, out_count, scratch_tiles, win,
+                                        num_cu, s, w1);
+        if (!per_rank) return hipMemsetAsync(out_count, 0, sizeof(uint32_t), s);
+        const uint32_t blocks = (uint32_t)std::max<size_t>(1, std::min<size_t>((per_rank + STG_WG - 1) / STG_WG,
+                                                                              (size_t)num_cu * 8));
+        win_mark_w<<<blocks, STG_WG, 0, s>>>(k.idx, per_rank, n, win, w1.desc ? w1.dup : nullptr,
+                                             w1.desc ? w1.ticket : nullptr, k.flag, wend);
+        if (w1.desc) {
+            constexpr uint32_t wp = 4;
+            const uint32_t nt1 = (uint32_t)((per_rank + wp * STG_WG - 1) / (wp * STG_WG));
+            Win1ArgsW a{{static_cast<const uint32_t *>(k.idx), static_cast<const float *>(k.val), per_rank, n, nt1, win,
+                         w1.desc, w1.ticket, 0ull, w1.tag, out_idx, out_val, out_count, w1.fail, w1.dup,
+                         w1.sgd != nullptr, w1.sgd ? *w1.sgd : SgdLaunch{}, w1.adam != nullptr,
+                         w1.adam ? *w1.adam : AdamLaunch{}},
+                        k.flag, wend};
+            if (a.fuse_sgd && a.sgd.last) win_emit1t<wp, true, true><<<nt1, STG_WG, 0, s>>>(a);
+            else win_emit1t<wp, false, true><<<nt1, STG_WG, 0, s>>>(a);
+            if (w1.grid_out) *w1.grid_out = nt1;
+            return hipGetLastError();
+        }
+        const uint32_t nt = (uint32_t)((per_rank + MARK_TILE - 1) / MARK_TILE);
+        win_count_w<<<nt, STG_WG, 0, s>>>(k.idx, per_rank, n, win, scratch_tiles, k.flag, wend);
+        const uint32_t G = std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)num_cu, nt));
+        win_emit1_w<<<G, STG_WG, 0, s>>>(k.idx, k.val, per_rank, n, nt, win, scratch_tiles, out_idx, out_val,
+                                         out_count, k.flag, wend);
+        return hipGetLastError();
+    }
+    if (per_rank) {
+        const uint32_t b2 = (uint32_t)std::max<size_t>(1, std::min<size_t>((2 * per_rank + STG_WG - 1) / STG_WG,
+                                                                           (size_t)num_cu * 8));
+        for (int r = 0; r <= world; ++r) {
+            const RankStream *sc = r >= 1 ? &ranks[r - 1] : nullptr, *mk = r < world ? &ranks[r] : nullptr;
+            uint32_t *swin = win + (size_t)((r - 1) & 1) * n, *mwin = win + (size_t)(r & 1) * n;
+            if (!(sc && sc->flag) && !(mk && mk->flag))  // both already u32 / f32
+                scatter_mark<<<b2, STG_WG, 0, s>>>(sc ? static_cast<const uint32_t *>(sc->idx) : nullptr,
+                                                   sc ? static_cast<const float *>(sc->val) : nullptr, swin,
+                                                   mk ? static_cast<const uint32_t *>(mk->idx) : nullptr, mwin,
+                                                   per_rank, n, dense, mark);
+            else
+                scatter_mark_w<<<b2, STG_WG, 0, s>>>(sc ? sc->idx : nullptr, sc ? sc->val : nullptr,
+                                                     sc ? sc->flag : 0u, swin, mk ? mk->idx : nullptr,
+                                                     mk ? mk->flag : 0u, mwin, per_rank, n, wend, dense, mark);
+        }
+    }
+    return launch_mark_emit(n, world, dense, mark, out_idx, out_val, out_count, scratch_tiles, s);
 }
 
 hipError_t launch_sgd(const SgdLaunch &a, hipStream_t s) {

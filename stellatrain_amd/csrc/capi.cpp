@@ -1035,9 +1035,49 @@ int stg_error_feedback_device(float *d_grad, size_t n, const uint32_t *d_idx, si
     return STG_OK;
 }
 
-int stg_scatter_merge_device(const uint32_t *d_idx, const float *d_val, size_t per_rank, int world, size_t n,
-                             float *d_dense, uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
-                             uint32_t *d_out_count, void *stream) {
+// The streams of one MERGE decompress: decoded pairs back to back (idx, val),
+// or `ranks` -- each rank's stream where it landed, in its wire form.
+struct MergeSrc {
+    const uint32_t *idx;
+    const float *val;
+    const stg_rank_stream_t *ranks;
+};
+
+static hipError_t launch_merge_src(const MergeSrc &src, size_t per_rank, int world, size_t n, float *dense,
+                                   uint8_t *mark, uint32_t *out_idx, float *out_val, uint32_t *out_count,
+                                   MergeScratch *ms, int ncu, hipStream_t s, const stg::Win1Desc &w1) {
+    if (!src.ranks)
+        return stg::launch_scatter_merge(src.idx, src.val, per_rank, world, n, dense, mark, out_idx, out_val,
+                                         out_count, ms->tiles, ms->win, ncu, s, w1);
+    std::vector<stg::RankStream> rs((size_t)world);
+    for (int r = 0; r < world; ++r) rs[r] = stg::RankStream{src.ranks[r].d_idx, src.ranks[r].d_val,
+                                                            (uint32_t)src.ranks[r].flag};
+    return stg::launch_scatter_merge_wire(rs.data(), per_rank, world, n, dense, mark, out_idx, out_val, out_count,
+                                          ms->tiles, ms->win, ncu, s, w1);
+}
+
+// The wire entries' argument checks: all before any device call.
+static int merge_wire_check(const stg_rank_stream_t *ranks, size_t per_rank, int world, const float *d_dense,
+                            const uint8_t *d_mark) {
+    if (world < 1) return fail(STG_ERR_INVALID, "world must be >= 1");
+    if (!ranks) return fail(STG_ERR_INVALID, "null rank stream array");
+    for (int r = 0; r < world; ++r) {
+        if (ranks[r].flag & ~(STG_WIRE_U16_IDX | STG_WIRE_F16_VAL))
+            return fail(STG_ERR_INVALID, "unknown wire flag bits in a rank stream");
+        if (per_rank && (!ranks[r].d_idx || !ranks[r].d_val)) return fail(STG_ERR_INVALID, "null rank stream buffer");
+        // a 16-bit buffer needs its 2-byte alignment, a 32-bit one its 4-byte alignment
+        if ((reinterpret_cast<uintptr_t>(ranks[r].d_idx) & (ranks[r].flag & STG_WIRE_U16_IDX ? 1u : 3u)) ||
+            (reinterpret_cast<uintptr_t>(ranks[r].d_val) & (ranks[r].flag & STG_WIRE_F16_VAL ? 1u : 3u)))
+            return fail(STG_ERR_INVALID, "rank stream buffer misaligned for its element type");
+    }
+    if (world > 1 && (!d_dense || !d_mark)) return fail(STG_ERR_INVALID, "dense/mark scratch required for world > 1");
+    if (world > 1 && (reinterpret_cast<uintptr_t>(d_mark) & 15u)) return fail(STG_ERR_INVALID, "mark scratch must be 16-byte aligned");
+    return STG_OK;
+}
+
+static int scatter_merge_src(const MergeSrc &src, size_t per_rank, int world, size_t n, float *d_dense,
+                             uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val, uint32_t *d_out_count,
+                             void *stream) {
     if (world < 1) return fail(STG_ERR_INVALID, "world must be >= 1");
     if (world > 1 && (!d_dense || !d_mark)) return fail(STG_ERR_INVALID, "dense/mark scratch required for world > 1");
     if (world > 1 && (reinterpret_cast<uintptr_t>(d_mark) & 15u)) return fail(STG_ERR_INVALID, "mark scratch must be 16-byte aligned");
@@ -1056,9 +1096,25 @@ int stg_scatter_merge_device(const uint32_t *d_idx, const float *d_val, size_t p
     uint32_t grid = 0;
     const stg::Win1Desc w1{ms->desc, ms->ticket, 0, ms->tag, &grid, ms->fail,
                            reinterpret_cast<uint32_t *>(ms->ticket + 1)};
-    HIP_TRY(stg::launch_scatter_merge(d_idx, d_val, per_rank, world, n, d_dense, d_mark, d_out_idx, d_out_val,
-                                      d_out_count, ms->tiles, ms->win, ncu, s, w1));
+    HIP_TRY(launch_merge_src(src, per_rank, world, n, d_dense, d_mark, d_out_idx, d_out_val, d_out_count, ms.get(),
+                             ncu, s, w1));
     return STG_OK;
+}
+
+int stg_scatter_merge_device(const uint32_t *d_idx, const float *d_val, size_t per_rank, int world, size_t n,
+                             float *d_dense, uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
+                             uint32_t *d_out_count, void *stream) {
+    return scatter_merge_src(MergeSrc{d_idx, d_val, nullptr}, per_rank, world, n, d_dense, d_mark, d_out_idx,
+                             d_out_val, d_out_count, stream);
+}
+
+int stg_scatter_merge_wire_device(const stg_rank_stream_t *ranks, size_t per_rank, int world, size_t n,
+                                  float *d_dense, uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
+                                  uint32_t *d_out_count, void *stream) {
+    int rc = merge_wire_check(ranks, per_rank, world, d_dense, d_mark);
+    if (rc) return rc;
+    return scatter_merge_src(MergeSrc{nullptr, nullptr, ranks}, per_rank, world, n, d_dense, d_mark, d_out_idx,
+                             d_out_val, d_out_count, stream);
 }
 
 int stg_scatter_merge_check(void *stream) {
@@ -1197,15 +1253,14 @@ int stg_sgd_optimize_raw_device(stg_sgd_t o, const char *name, float *d_param, u
     return STG_OK;
 }
 
-int stg_merge_optimize_sgd_device(stg_sgd_t o, const char *name, float *d_param, uint32_t param_len,
-                                  const uint32_t *d_idx, const float *d_val, size_t per_rank, int world,
-                                  float *d_dense, uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
-                                  uint32_t *d_out_count, void *stream) {
+static int merge_optimize_sgd_src(stg_sgd_t o, const char *name, float *d_param, uint32_t param_len,
+                                  const MergeSrc &src, size_t per_rank, int world, float *d_dense, uint8_t *d_mark,
+                                  uint32_t *d_out_idx, float *d_out_val, uint32_t *d_out_count, void *stream) {
     if (!o || !name) return fail(STG_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(o->device));
     if (world != 1 || per_rank == 0) {  // the merge of several ranks, then the step over its output
-        int rc = stg_scatter_merge_device(d_idx, d_val, per_rank, world, param_len, d_dense, d_mark, d_out_idx,
-                                          d_out_val, d_out_count, stream);
+        int rc = scatter_merge_src(src, per_rank, world, param_len, d_dense, d_mark, d_out_idx, d_out_val,
+                                   d_out_count, stream);
         if (rc) return rc;
         const size_t cap = per_rank * (size_t)world;
         return stg_sgd_optimize_raw_device(o, name, d_param, param_len, d_out_val, d_out_idx,
@@ -1228,9 +1283,28 @@ int stg_merge_optimize_sgd_device(stg_sgd_t o, const char *name, float *d_param,
     uint32_t grid = 0;
     stg::Win1Desc w1{ms->desc, ms->ticket, 0, ms->tag, &grid, ms->fail, reinterpret_cast<uint32_t *>(ms->ticket + 1)};
     w1.sgd = &a;
-    HIP_TRY(stg::launch_scatter_merge(d_idx, d_val, per_rank, world, param_len, d_dense, d_mark, d_out_idx, d_out_val,
-                                      d_out_count, ms->tiles, ms->win, ncu, s, w1));
+    HIP_TRY(launch_merge_src(src, per_rank, world, param_len, d_dense, d_mark, d_out_idx, d_out_val, d_out_count,
+                             ms.get(), ncu, s, w1));
     return STG_OK;
+}
+
+int stg_merge_optimize_sgd_device(stg_sgd_t o, const char *name, float *d_param, uint32_t param_len,
+                                  const uint32_t *d_idx, const float *d_val, size_t per_rank, int world,
+                                  float *d_dense, uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
+                                  uint32_t *d_out_count, void *stream) {
+    return merge_optimize_sgd_src(o, name, d_param, param_len, MergeSrc{d_idx, d_val, nullptr}, per_rank, world,
+                                  d_dense, d_mark, d_out_idx, d_out_val, d_out_count, stream);
+}
+
+int stg_merge_optimize_sgd_wire_device(stg_sgd_t o, const char *name, float *d_param, uint32_t param_len,
+                                       const stg_rank_stream_t *ranks, size_t per_rank, int world, float *d_dense,
+                                       uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
+                                       uint32_t *d_out_count, void *stream) {
+    if (!o || !name) return fail(STG_ERR_INVALID, "null argument");
+    int rc = merge_wire_check(ranks, per_rank, world, d_dense, d_mark);
+    if (rc) return rc;
+    return merge_optimize_sgd_src(o, name, d_param, param_len, MergeSrc{nullptr, nullptr, ranks}, per_rank, world,
+                                  d_dense, d_mark, d_out_idx, d_out_val, d_out_count, stream);
 }
 
 int stg_sgd_get_momentum(stg_sgd_t o, const char *name, float *host_out, uint32_t len, void *stream) {
@@ -1431,15 +1505,14 @@ int stg_adam_optimize_raw_device(stg_adam_t o, const char *name, float *d_param,
     return STG_OK;
 }
 
-int stg_merge_optimize_adam_device(stg_adam_t o, const char *name, float *d_param, uint32_t param_len,
-                                   const uint32_t *d_idx, const float *d_val, size_t per_rank, int world,
-                                   float *d_dense, uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
-                                   uint32_t *d_out_count, void *stream) {
+static int merge_optimize_adam_src(stg_adam_t o, const char *name, float *d_param, uint32_t param_len,
+                                   const MergeSrc &src, size_t per_rank, int world, float *d_dense, uint8_t *d_mark,
+                                   uint32_t *d_out_idx, float *d_out_val, uint32_t *d_out_count, void *stream) {
     if (!o || !name) return fail(STG_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(o->device));
     if (world != 1 || per_rank == 0 || o->amsgrad) {  // the merge, then the step over its output
-        int rc = stg_scatter_merge_device(d_idx, d_val, per_rank, world, param_len, d_dense, d_mark, d_out_idx,
-                                          d_out_val, d_out_count, stream);
+        int rc = scatter_merge_src(src, per_rank, world, param_len, d_dense, d_mark, d_out_idx, d_out_val,
+                                   d_out_count, stream);
         if (rc) return rc;
         const size_t cap = std::min<size_t>(per_rank * (size_t)world, o->amsgrad ? param_len : 0xffffffffu);
         return stg_adam_optimize_raw_device(o, name, d_param, param_len, d_out_val, d_out_idx, (uint32_t)cap,
@@ -1461,9 +1534,28 @@ int stg_merge_optimize_adam_device(stg_adam_t o, const char *name, float *d_para
     uint32_t grid = 0;
     stg::Win1Desc w1{ms->desc, ms->ticket, 0, ms->tag, &grid, ms->fail, reinterpret_cast<uint32_t *>(ms->ticket + 1)};
     w1.adam = &a;
-    HIP_TRY(stg::launch_scatter_merge(d_idx, d_val, per_rank, world, param_len, d_dense, d_mark, d_out_idx, d_out_val,
-                                      d_out_count, ms->tiles, ms->win, ncu, s, w1));
+    HIP_TRY(launch_merge_src(src, per_rank, world, param_len, d_dense, d_mark, d_out_idx, d_out_val, d_out_count,
+                             ms.get(), ncu, s, w1));
     return STG_OK;
+}
+
+int stg_merge_optimize_adam_device(stg_adam_t o, const char *name, float *d_param, uint32_t param_len,
+                                   const uint32_t *d_idx, const float *d_val, size_t per_rank, int world,
+                                   float *d_dense, uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
+                                   uint32_t *d_out_count, void *stream) {
+    return merge_optimize_adam_src(o, name, d_param, param_len, MergeSrc{d_idx, d_val, nullptr}, per_rank, world,
+                                   d_dense, d_mark, d_out_idx, d_out_val, d_out_count, stream);
+}
+
+int stg_merge_optimize_adam_wire_device(stg_adam_t o, const char *name, float *d_param, uint32_t param_len,
+                                        const stg_rank_stream_t *ranks, size_t per_rank, int world, float *d_dense,
+                                        uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
+                                        uint32_t *d_out_count, void *stream) {
+    if (!o || !name) return fail(STG_ERR_INVALID, "null argument");
+    int rc = merge_wire_check(ranks, per_rank, world, d_dense, d_mark);
+    if (rc) return rc;
+    return merge_optimize_adam_src(o, name, d_param, param_len, MergeSrc{nullptr, nullptr, ranks}, per_rank, world,
+                                   d_dense, d_mark, d_out_idx, d_out_val, d_out_count, stream);
 }
 
 int stg_adam_get_state(stg_adam_t o, const char *name, float *host_m, float *host_v, uint32_t len,
@@ -1594,6 +1686,45 @@ int stg_wire_decode_device(const void *d_idx_in, const void *d_val_in, size_t nu
     HIP_TRY(stg::launch_wire_decode(d_idx_in, d_val_in, numel, (uint32_t)flag, d_idx, d_val, ncu,
                                     static_cast<hipStream_t>(stream)));
     return STG_OK;
+}
+
+int stg_wire_decode_batch_device(const stg_wire_rx_t *streams, size_t nstreams, void *stream) {
+    if (nstreams && !streams) return fail(STG_ERR_INVALID, "null stream array");
+    for (size_t i = 0; i < nstreams; ++i) {
+        const stg_wire_rx_t &w = streams[i];
+        if (w.flag & ~(STG_WIRE_U16_IDX | STG_WIRE_F16_VAL)) return fail(STG_ERR_INVALID, "unknown wire flag bits");
+        if (w.numel && (!w.d_idx_in || !w.d_val_in || !w.d_idx || !w.d_val))
+            return fail(STG_ERR_INVALID, "null argument");
+        if (w.numel > (size_t)STG_WG * 0xffffffull) return fail(STG_ERR_UNSUPPORTED, "wire stream too long for a batch");
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    stg::WireRxBatch b{};
+    uint64_t blocks = 0;
+    auto flush = [&]() -> int {
+        if (b.nb) HIP_TRY(stg::launch_wire_decode_batch(b, (uint32_t)blocks, s));
+        b = stg::WireRxBatch{};
+        blocks = 0;
+        return STG_OK;
+    };
+    for (size_t i = 0; i < nstreams; ++i) {
+        const stg_wire_rx_t &w = streams[i];
+        if (!w.numel) continue;
+        const uint64_t nbk = (w.numel + STG_WG - 1) / STG_WG;
+        if (b.nb == stg::WIRE_BATCH || blocks + nbk > 0x7fffffffull) {
+            int rc = flush();
+            if (rc) return rc;
+        }
+        stg::WireRx &d = b.b[b.nb++];
+        d.idx_in = w.d_idx_in;
+        d.val_in = w.d_val_in;
+        d.idx = w.d_idx;
+        d.val = w.d_val;
+        d.n = w.numel;
+        d.flag = (uint32_t)w.flag;
+        d.blk0 = (uint32_t)blocks;
+        blocks += nbk;
+    }
+    return flush();
 }
 
 int stg_synth_fill_device(float *d_dst, size_t n, uint64_t seed, int dist, uint32_t param, void *stream) {

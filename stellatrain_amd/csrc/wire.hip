@@ -64,18 +64,21 @@ __global__ void __launch_bounds__(STG_WG) wire_decode(const void *__restrict__ i
                                                       uint32_t *__restrict__ idx, float *__restrict__ val) {
     const size_t stride = (size_t)gridDim.x * STG_WG;
     for (size_t i = (size_t)blockIdx.x * STG_WG + threadIdx.x; i < n; i += stride) {
-        if (flag & 1u) {
-            const uint16_t w = static_cast<const uint16_t *>(idx_in)[i];
-            idx[i] = i < simd_end ? (uint32_t)(int32_t)(int16_t)w : (uint32_t)w;
-        } else {
-            idx[i] = static_cast<const uint32_t *>(idx_in)[i];
-        }
-        if (flag & 2u) {
-            const uint16_t h = static_cast<const uint16_t *>(val_in)[i];
-            val[i] = i < simd_end ? __uint_as_float(f16_to_f32(h)) : (float)h;
-        } else {
-            val[i] = static_cast<const float *>(val_in)[i];
-        }
+        idx[i] = wire_get_idx(idx_in, flag, simd_end, i);
+        val[i] = wire_get_val(val_in, flag, simd_end, i);
+    }
+}
+
+// Batched decode: workgroups dealt to the streams as in wire_encode_batch.
+__global__ void __launch_bounds__(STG_WG) wire_decode_batch(WireRxBatch w) {
+    uint32_t b = 0;
+    while (b + 1 < w.nb && blockIdx.x >= w.b[b + 1].blk0) ++b;
+    const WireRx &d = w.b[b];
+    const size_t i = (size_t)(blockIdx.x - d.blk0) * STG_WG + threadIdx.x;
+    if (i < d.n) {
+        const size_t wend = 8 * ((d.n - 1) / 8);
+        d.idx[i] = wire_get_idx(d.idx_in, d.flag, wend, i);
+        d.val[i] = wire_get_val(d.val_in, d.flag, wend, i);
     }
 }
 
@@ -96,6 +99,12 @@ hipError_t launch_wire_encode(const uint32_t *idx, const float *val, size_t n, u
 hipError_t launch_wire_decode(const void *idx_in, const void *val_in, size_t n, uint32_t flag, uint32_t *idx,
                               float *val, int num_cu, hipStream_t s) {
     wire_decode<<<wire_blocks(n, num_cu), STG_WG, 0, s>>>(idx_in, val_in, n, simd_end(n), flag, idx, val);
+    return hipGetLastError();
+}
+
+hipError_t launch_wire_decode_batch(const WireRxBatch &w, uint32_t blocks, hipStream_t s) {
+    if (!w.nb || !blocks) return hipSuccess;
+    wire_decode_batch<<<blocks, STG_WG, 0, s>>>(w);
     return hipGetLastError();
 }
 

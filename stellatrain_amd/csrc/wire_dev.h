@@ -65,6 +65,76 @@ __device__ __forceinline__ uint32_t wire_val16(float f, size_t i, size_t wend) {
     return i < wend ? f32_to_f16_rne(__float_as_uint(f)) : f32_to_u16_trunc(f);
 }
 
+// The receiver's inverse (comm_manager.cpp:877-906) of a 16-bit wire word at
+// position i: blocks sign-extend (_mm256_cvtepi16_epi32), the tail zero-extends
+__device__ __forceinline__ uint32_t wire_idx32(uint32_t w, size_t i, size_t wend) {
+    return i < wend ? (uint32_t)(int32_t)(int16_t)w : w;
+}
+// blocks widen the fp16 exactly, the tail is (float) of the 16-bit integer
+__device__ __forceinline__ float wire_val32(uint32_t h, size_t i, size_t wend) {
+    return i < wend ? __uint_as_float(f16_to_f32(h)) : (float)h;
+}
+
+// Pair i of a received stream in the form `flag` says it arrived in.
+__device__ __forceinline__ uint32_t wire_get_idx(const void *idx, uint32_t flag, size_t wend, size_t i) {
+    return flag & 1u ? wire_idx32(static_cast<const uint16_t *>(idx)[i], i, wend) : static_cast<const uint32_t *>(idx)[i];
+}
+__device__ __forceinline__ float wire_get_val(const void *val, uint32_t flag, size_t wend, size_t i) {
+    return flag & 2u ? wire_val32(static_cast<const uint16_t *>(val)[i], i, wend) : static_cast<const float *>(val)[i];
+}
+
+// Pairs g..g+3 of a received stream of m >= 1 pairs (g % 4 == 0, so all four
+// sit on one side of wend): one 8-byte load of the 16-bit form (16-byte of the
+// 32-bit form) when the four exist and their address is that aligned, else
+// single loads with the position clamped to m - 1 (a received message ends
+// there; the caller masks what it reads past m).
+__device__ __forceinline__ void wire_get_idx4(const void *idx, uint32_t flag, size_t wend, size_t m, size_t g,
+                                              uint32_t *j) {
+    if (flag & 1u) {
+        const uint16_t *p = static_cast<const uint16_t *>(idx) + g;
+        if (g + 4 <= m && (reinterpret_cast<uintptr_t>(p) & 7u) == 0) {
+            const uint2 v = *reinterpret_cast<const uint2 *>(p);
+            j[0] = wire_idx32(v.x & 0xffffu, g, wend); j[1] = wire_idx32(v.x >> 16, g, wend);
+            j[2] = wire_idx32(v.y & 0xffffu, g, wend); j[3] = wire_idx32(v.y >> 16, g, wend);
+        } else {
+#pragma unroll
+            for (uint32_t b = 0; b < 4; ++b) j[b] = wire_get_idx(idx, flag, wend, g + b < m ? g + b : m - 1);
+        }
+    } else {
+        const uint32_t *p = static_cast<const uint32_t *>(idx) + g;
+        if (g + 4 <= m && (reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(p);
+            j[0] = v.x; j[1] = v.y; j[2] = v.z; j[3] = v.w;
+        } else {
+#pragma unroll
+            for (uint32_t b = 0; b < 4; ++b) j[b] = static_cast<const uint32_t *>(idx)[g + b < m ? g + b : m - 1];
+        }
+    }
+}
+__device__ __forceinline__ void wire_get_val4(const void *val, uint32_t flag, size_t wend, size_t m, size_t g,
+                                              float *v) {
+    if (flag & 2u) {
+        const uint16_t *p = static_cast<const uint16_t *>(val) + g;
+        if (g + 4 <= m && (reinterpret_cast<uintptr_t>(p) & 7u) == 0) {
+            const uint2 x = *reinterpret_cast<const uint2 *>(p);
+            v[0] = wire_val32(x.x & 0xffffu, g, wend); v[1] = wire_val32(x.x >> 16, g, wend);
+            v[2] = wire_val32(x.y & 0xffffu, g, wend); v[3] = wire_val32(x.y >> 16, g, wend);
+        } else {
+#pragma unroll
+            for (uint32_t b = 0; b < 4; ++b) v[b] = wire_get_val(val, flag, wend, g + b < m ? g + b : m - 1);
+        }
+    } else {
+        const float *p = static_cast<const float *>(val) + g;
+        if (g + 4 <= m && (reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
+            const float4 x = *reinterpret_cast<const float4 *>(p);
+            v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+        } else {
+#pragma unroll
+            for (uint32_t b = 0; b < 4; ++b) v[b] = static_cast<const float *>(val)[g + b < m ? g + b : m - 1];
+        }
+    }
+}
+
 // Pair `o` of the stream in the form `flag` selects (STG_WIRE_U16_IDX = 1,
 // STG_WIRE_F16_VAL = 2; 0: the codec's own u32 / f32).
 __device__ __forceinline__ void wire_put(uint32_t *idx, float *val, uint32_t flag, uint32_t wend, uint32_t o,

@@ -372,6 +372,17 @@ hipError_t launch_scatter_merge(const uint32_t *idx, const float *val, size_t pe
                                 uint32_t *out_count, uint32_t *scratch_tiles, uint32_t *win, int num_cu,
                                 hipStream_t s, const Win1Desc &w1);
 constexpr uint32_t MERGE_TILE = STG_WG * 16;  // pairs / marks per scatter-merge tile
+// The same merge reading each rank's stream where it landed, in the form its
+// flag says it arrived in (STG_WIRE_* bits; wire_dev.h): ranks[r] holds
+// per_rank pairs.  Streams with flag 0 take the decoded kernels.
+struct RankStream {
+    const void *idx, *val;
+    uint32_t flag;
+};
+hipError_t launch_scatter_merge_wire(const RankStream *ranks, size_t per_rank, int world, size_t n, float *dense,
+                                     uint8_t *mark, uint32_t *out_idx, float *out_val, uint32_t *out_count,
+                                     uint32_t *scratch_tiles, uint32_t *win, int num_cu, hipStream_t s,
+                                     const Win1Desc &w1);
 
 struct SgdLaunch {
     float *param;
@@ -428,6 +439,18 @@ struct WireBatch {
     uint32_t nb;
 };
 hipError_t launch_wire_encode_batch(const WireBatch &w, uint32_t blocks, hipStream_t s);
+struct WireRx {  // one received stream of a batched decode
+    const void *idx_in, *val_in;
+    uint32_t *idx;
+    float *val;
+    uint64_t n;
+    uint32_t flag, blk0;  // blk0: first workgroup of this stream in the launch
+};
+struct WireRxBatch {
+    WireRx b[WIRE_BATCH];
+    uint32_t nb;
+};
+hipError_t launch_wire_decode_batch(const WireRxBatch &w, uint32_t blocks, hipStream_t s);
 hipError_t launch_wire_encode(const uint32_t *idx, const float *val, size_t n, uint32_t flag, void *idx_out,
                               void *val_out, int num_cu, hipStream_t s);
 hipError_t launch_wire_decode(const void *idx_in, const void *val_in, size_t n, uint32_t flag, uint32_t *idx,

@@ -20,10 +20,11 @@ import ctypes as C
 
 import numpy as np
 
-from ._capi import CodecError, check, lib
+from ._capi import CodecError, StgRankStream, StgWireRx, check, lib
 from .compressor import Compressor, make_compressor
 
-__all__ = ["CodecEngine", "SparseSGD", "merge_numel", "api_numel", "scatter_merge", "owner_of"]
+__all__ = ["CodecEngine", "SparseSGD", "merge_numel", "api_numel", "scatter_merge", "scatter_merge_wire",
+           "wire_decode_batch", "owner_of"]
 
 
 def merge_numel(n: int, ratio: float, world: int = 1) -> int:
@@ -269,12 +270,61 @@ def wire_decode(widx, wval, flag: int, idx=None, val=None):
     return idx, val
 
 
-def _merge_optimize(fn, h, param, name, idx, val, per_rank, world, dense, mark, out_idx, out_val, count):
-    """ModuleCpuOptimize::run through one C call (``fn``): the MERGE decompress
-    of ``world`` rank streams into the merged stream (returned), then the
-    optimizer's step on it."""
+def _wire_dtypes(flag: int):
     import torch
-    dev, n = param.device, param.numel()
+    if flag not in (0, 1, 2, 3):
+        raise ValueError(f"wire flag {flag!r} outside 0..3")
+    return (torch.int16 if flag & WIRE_U16_IDX else torch.int32,
+            torch.int16 if flag & WIRE_F16_VAL else torch.float32)
+
+
+def wire_decode_batch(items):
+    """Batched wire decode (``stg_wire_decode_batch_device``): items of
+    (widx, wval, flag, idx_out, val_out) device tensors; the same bytes as
+    ``wire_decode`` on each, in launches of up to 16 streams."""
+    import torch
+    if not items:
+        return
+    arr = (StgWireRx * len(items))()
+    for j, (wi, wv, flag, io, vo) in enumerate(items):
+        flag = int(flag)
+        di, dv = _wire_dtypes(flag)
+        n = wi.numel()
+        if wi.dtype != di or wv.dtype != dv or io.dtype != torch.int32 or vo.dtype != torch.float32:
+            raise ValueError(f"wire_decode_batch: item {j}: dtypes do not match flag {flag}")
+        if not all(t.is_contiguous() for t in (wi, wv, io, vo)):
+            raise ValueError(f"wire_decode_batch: item {j}: tensors must be contiguous")
+        if wv.numel() < n or io.numel() < n or vo.numel() < n:
+            raise ValueError(f"wire_decode_batch: item {j}: a tensor is shorter than the stream")
+        arr[j] = StgWireRx(wi.data_ptr(), wv.data_ptr(), n, flag, io.data_ptr(), vo.data_ptr())
+    dev = items[0][0].device
+    check(lib().stg_wire_decode_batch_device(arr, len(items),
+                                             C.c_void_p(torch.cuda.current_stream(dev.index).cuda_stream)))
+
+
+def _rank_streams(streams, per_rank: int):
+    """The ``stg_rank_stream_t`` array of a list of (widx, wval, flag) device
+    tensors, after checking dtype against flag, contiguity and length."""
+    if not streams:
+        raise ValueError("at least one rank stream is required")
+    arr = (StgRankStream * len(streams))()
+    for r, (wi, wv, flag) in enumerate(streams):
+        flag = int(flag)
+        di, dv = _wire_dtypes(flag)
+        if wi.dtype != di or wv.dtype != dv:
+            raise ValueError(f"rank {r}: dtypes {wi.dtype}/{wv.dtype} do not match wire flag {flag}")
+        if not wi.is_contiguous() or not wv.is_contiguous():
+            raise ValueError(f"rank {r}: stream tensors must be contiguous")
+        if wi.numel() < per_rank or wv.numel() < per_rank:
+            raise ValueError(f"rank {r}: stream shorter than per_rank = {per_rank}")
+        if wi.device != streams[0][0].device or wv.device != wi.device:
+            raise ValueError(f"rank {r}: stream tensors on different devices")
+        arr[r] = StgRankStream(wi.data_ptr(), wv.data_ptr(), flag)
+    return arr
+
+
+def _merge_outputs(dev, n, per_rank, world, dense, mark, out_idx, out_val, count):
+    import torch
     if out_idx is None:
         out_idx = torch.empty(per_rank * world, dtype=torch.int32, device=dev)
     if out_val is None:
@@ -288,6 +338,48 @@ def _merge_optimize(fn, h, param, name, idx, val, per_rank, world, dense, mark, 
             mark = torch.zeros(n, dtype=torch.uint8, device=dev)
     dp = C.c_void_p(dense.data_ptr()) if dense is not None else None
     mp = C.c_void_p(mark.data_ptr()) if mark is not None else None
+    return dp, mp, out_idx, out_val, count
+
+
+def scatter_merge_wire(streams, per_rank: int, n: int, dense=None, mark=None, out_idx=None, out_val=None,
+                       count=None):
+    """MERGE decompress straight from received streams: ``streams`` is one
+    (widx, wval, flag) per rank, each where it landed and in the form it
+    arrived in (int16-typed tensors for the 16-bit forms, as ``wire_encode``
+    returns them).  The result is bitwise that of ``wire_decode`` per rank
+    into one buffer followed by ``scatter_merge``, without the decode launches
+    and the buffer.  ``dense`` / ``mark`` as in ``scatter_merge``."""
+    import torch
+    world = len(streams)
+    arr = _rank_streams(streams, per_rank)
+    dev = streams[0][0].device
+    dp, mp, out_idx, out_val, count = _merge_outputs(dev, n, per_rank, world, dense, mark, out_idx, out_val, count)
+    check(lib().stg_scatter_merge_wire_device(arr, per_rank, world, n, dp, mp, C.c_void_p(out_idx.data_ptr()),
+                                              C.c_void_p(out_val.data_ptr()), C.c_void_p(count.data_ptr()),
+                                              C.c_void_p(torch.cuda.current_stream(dev.index).cuda_stream)))
+    return out_idx, out_val, count
+
+
+def _merge_optimize_wire(fn, h, param, name, streams, per_rank, dense, mark, out_idx, out_val, count):
+    """``_merge_optimize`` on received streams (``scatter_merge_wire``'s form)."""
+    import torch
+    world = len(streams)
+    arr = _rank_streams(streams, per_rank)
+    dev, n = param.device, param.numel()
+    dp, mp, out_idx, out_val, count = _merge_outputs(dev, n, per_rank, world, dense, mark, out_idx, out_val, count)
+    check(fn(h, name.encode(), C.c_void_p(param.data_ptr()), n, arr, per_rank, world, dp, mp,
+             C.c_void_p(out_idx.data_ptr()), C.c_void_p(out_val.data_ptr()), C.c_void_p(count.data_ptr()),
+             C.c_void_p(torch.cuda.current_stream(dev.index).cuda_stream)))
+    return out_idx, out_val, count
+
+
+def _merge_optimize(fn, h, param, name, idx, val, per_rank, world, dense, mark, out_idx, out_val, count):
+    """ModuleCpuOptimize::run through one C call (``fn``): the MERGE decompress
+    of ``world`` rank streams into the merged stream (returned), then the
+    optimizer's step on it."""
+    import torch
+    dev, n = param.device, param.numel()
+    dp, mp, out_idx, out_val, count = _merge_outputs(dev, n, per_rank, world, dense, mark, out_idx, out_val, count)
     check(fn(h, name.encode(), C.c_void_p(param.data_ptr()), n, C.c_void_p(idx.data_ptr()), C.c_void_p(val.data_ptr()),
              per_rank, world, dp, mp, C.c_void_p(out_idx.data_ptr()), C.c_void_p(out_val.data_ptr()),
              C.c_void_p(count.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev.index).cuda_stream)))
@@ -369,6 +461,14 @@ class SparseSGD:
         return _merge_optimize(lib().stg_merge_optimize_sgd_device, self._h, param, name, idx, val, per_rank, world,
                                dense, mark, out_idx, out_val, count)
 
+    def merge_optimize_wire(self, param, name: str, streams, per_rank: int, dense=None, mark=None, out_idx=None,
+                            out_val=None, count=None):
+        """``merge_optimize`` straight from received streams, one (widx, wval,
+        flag) per rank as in ``scatter_merge_wire``; bitwise the result of
+        ``wire_decode`` per rank followed by ``merge_optimize``."""
+        return _merge_optimize_wire(lib().stg_merge_optimize_sgd_wire_device, self._h, param, name, streams, per_rank,
+                                    dense, mark, out_idx, out_val, count)
+
     def momentum_buffer(self, name: str, n: int):
         import torch
         out = np.zeros(n, np.float32)
@@ -415,6 +515,13 @@ class SparseAdam:
         emission at world 1 without amsgrad, else the two calls."""
         return _merge_optimize(lib().stg_merge_optimize_adam_device, self._h, param, name, idx, val, per_rank, world,
                                dense, mark, out_idx, out_val, count)
+
+    def merge_optimize_wire(self, param, name: str, streams, per_rank: int, dense=None, mark=None, out_idx=None,
+                            out_val=None, count=None):
+        """``merge_optimize`` straight from received streams (see
+        ``SparseSGD.merge_optimize_wire``)."""
+        return _merge_optimize_wire(lib().stg_merge_optimize_adam_wire_device, self._h, param, name, streams,
+                                    per_rank, dense, mark, out_idx, out_val, count)
 
     def check_device(self) -> None:
         """Raise if a device-side failure was flagged (amsgrad look-back timeout)."""

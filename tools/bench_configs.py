@@ -17,6 +17,8 @@ times the other configs on one GPU and prints one JSON line per measurement:
       and the same with sparse Adam (plain and amsgrad) as the apply;
   APPLY  the optimizer applies alone on a 64 MiB param (k = 167,772 pairs
       from the codec), and WIRE encode/decode of that stream (u16 idx, fp16 val);
+  WMERGE  merge_optimize straight from wire-form rank streams against one
+      wire_decode per rank plus the decoded call (60,000 floats and 64 MiB);
   E2E thresholdv16 64 MiB host-inclusive (serial and overlapped).
 
 Every device timing rotates over >= 512 MB of distinct buckets so the 256 MB
@@ -560,6 +562,54 @@ def wire_fused(torch, calls):
     return out
 
 
+def wire_merge(torch, calls):
+    """ModuleCpuOptimize::run on received streams: merge_optimize_wire (SGD)
+    against the sequence it replaces -- one wire_decode per rank into a
+    concatenation buffer, then merge_optimize -- same process, same inputs.
+    The 60,000-float tensor with u16 indices (flags 1 and 3) at world 1, 2, 8
+    and the 64 MiB bucket (k = 167,772 per rank; flags 0 and 2) at world 1, 8.
+    Each rank's indices are a distinct sorted sample of the tensor, packed by
+    wire_encode; every rank buffer is a tensor of its own."""
+    from stellatrain_amd import merge_numel, wire_decode, wire_encode
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev)
+    out = []
+    for n, flags, worlds in ((60000, (1, 3), (1, 2, 8)), (16 << 20, (0, 2), (1, 8))):
+        k = merge_numel(n, 0.99)
+        dense = torch.zeros(n, dtype=torch.float32, device=dev)
+        mark = torch.zeros(n, dtype=torch.uint8, device=dev)
+        for flag in flags:
+            for world in worlds:
+                g = torch.Generator(device="cpu").manual_seed(11)
+                ranks = []
+                for _ in range(world):
+                    idx = torch.sort(torch.randperm(n, generator=g)[:k]).values.to(torch.int32).to(dev)
+                    val = torch.randn(k, generator=g).to(dev)
+                    wi, wv = wire_encode(idx, val, flag)
+                    ranks.append((wi, wv, flag))
+                di = torch.empty(world * k, dtype=torch.int32, device=dev)
+                dv = torch.empty(world * k, dtype=torch.float32, device=dev)
+                oi, ov = torch.empty_like(di), torch.empty_like(dv)
+                oc = torch.empty(1, dtype=torch.int32, device=dev)
+                param = torch.zeros(n, dtype=torch.float32, device=dev)
+                row = {"config": f"WMERGE merge_optimize SGD(m=0.9) n={n} k={k} per rank, wire flag {flag}, "
+                                 f"world={world}"}
+                for wire in (True, False):
+                    opt, _ = make_opt("sgd")
+
+                    def step(s):
+                        if wire:
+                            opt.merge_optimize_wire(param, "wm@w", ranks, k, dense, mark, oi, ov, oc)
+                        else:
+                            for r, (wi, wv, f) in enumerate(ranks):
+                                wire_decode(wi, wv, f, di[r * k:(r + 1) * k], dv[r * k:(r + 1) * k])
+                            opt.merge_optimize(param, "wm@w", di, dv, k, world, dense, mark, oi, ov, oc)
+                    row["wire_us" if wire else "separate_us"] = round(_time_loop(torch, st, step, calls, 8), 2)
+                row["union"] = int(oc.item())
+                out.append(row)
+    return out
+
+
 def cpu_codec(method, mib, ratio, seconds):
     """The reference CPU path beside its GPU row, same run, this host's cores
     (north_star): oracle/_ref/libstg_ref.so (the reference's compress/*.cpp
@@ -630,7 +680,7 @@ def main():
     p.add_argument("--calls", type=int, default=48)
     p.add_argument("--c4-streams", type=int, default=4)
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="per CPU baseline row (0: none)")
-    p.add_argument("--only", default="c2,c3,c4,c5,single,e2e,apply,merge,ef,gather,gfused,wfused")
+    p.add_argument("--only", default="c2,c3,c4,c5,single,e2e,apply,merge,ef,gather,gfused,wfused,wmerge")
     a = p.parse_args()
     import torch
     from stellatrain_amd import make_compressor
@@ -675,6 +725,9 @@ def main():
             emit(merge_world(torch, a.calls, w))
     if "apply" in only:
         for d in apply_and_wire(torch, a.calls):
+            emit(d)
+    if "wmerge" in only:
+        for d in wire_merge(torch, a.calls):
             emit(d)
 
 
