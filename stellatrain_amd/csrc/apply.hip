@@ -240,10 +240,6 @@ __global__ void __launch_bounds__(STG_WG) mark_emit_tile(uint8_t *__restrict__ m
     }
 }
 
-
-constexpr uint32_t WPER = MARK_TILE / STG_WG;  // 16 consecutive pairs per lane
-static_assert(WPER == 16, "four uint4 of indices per lane");
-
 // WIRE: the lane's WP pairs (e % 4 == 0, WP % 4 == 0) of a received stream,
 // four at a time (wire_dev.h: an 8-byte load of the 16-bit form where the four
 // exist and are aligned, clamped single loads otherwise).
@@ -262,10 +258,10 @@ __device__ __forceinline__ void wire_val_wp(const void *val, uint32_t flag, size
     for (uint32_t q = 0; q < WP / 4; ++q) wire_get_val4(val, flag, wend, m, e + 4 * q, &v[4 * q]);
 }
 
-// The lane's 16 pairs e .. e+15: their indices, and which of them win (bit b).
-// Every load is issued before any is used -- the 16 index loads together,
-// then the 16 winner words (clamped addresses, results masked) -- two round
-// trips per lane instead of 32 dependent ones.
+// The lane's WP pairs e .. e+WP-1: their indices, and which of them win (bit b).
+// Every load is issued before any is used -- the index loads together, then
+// the winner words (clamped addresses, results masked) -- two round trips per
+// lane instead of 2 WP dependent ones.
 template <uint32_t WP, bool WIRE = false>
 __device__ __forceinline__ uint32_t win_keep_t(const uint32_t *__restrict__ idx, size_t m, size_t n,
                                                const uint32_t *__restrict__ win, size_t e, uint32_t (&j)[WP],
@@ -292,116 +288,7 @@ __device__ __forceinline__ uint32_t win_keep_t(const uint32_t *__restrict__ idx,
         if (e + b < m && j[b] < n && w[b] == (uint32_t)(e + b) + 1u) keep |= 1u << b;
     return keep;
 }
-template <bool WIRE>
-__device__ __forceinline__ uint32_t win_keep(const uint32_t *__restrict__ idx, size_t m, size_t n,
-                                             const uint32_t *__restrict__ win, size_t e, uint32_t (&j)[WPER],
-                                             uint32_t flag, size_t wend) {
-    return win_keep_t<WPER, WIRE>(idx, m, n, win, e, j, flag, wend);
-}
 
-// world == 1, pass 1: winners per tile of MARK_TILE pairs.
-template <bool WIRE>
-__device__ __forceinline__ void win_count_body(const uint32_t *__restrict__ idx, size_t m, size_t n,
-                                               const uint32_t *__restrict__ win, uint32_t *__restrict__ tile_cnt,
-                                               uint32_t flag, size_t wend) {
-    __shared__ uint32_t s[STG_WAVES];
-    const size_t e = (size_t)blockIdx.x * MARK_TILE + (size_t)WPER * threadIdx.x;
-    uint32_t j[WPER];
-    uint32_t c = e < m ? (uint32_t)__popc(win_keep<WIRE>(idx, m, n, win, e, j, flag, wend)) : 0u;
-    c = wave_sum(c);
-    if (__lane_id() == 0) s[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (uint32_t w = 0; w < STG_WAVES; ++w) t += s[w];
-        tile_cnt[blockIdx.x] = t;
-    }
-}
-__global__ void __launch_bounds__(STG_WG) win_count(const uint32_t *__restrict__ idx, size_t m, size_t n,
-                                                    const uint32_t *__restrict__ win, uint32_t *__restrict__ tile_cnt) {
-    win_count_body<false>(idx, m, n, win, tile_cnt, 0u, 0);
-}
-__global__ void __launch_bounds__(STG_WG) win_count_w(const void *__restrict__ idx, size_t m, size_t n,
-                                                      const uint32_t *__restrict__ win,
-                                                      uint32_t *__restrict__ tile_cnt, uint32_t flag, size_t wend) {
-    win_count_body<true>(static_cast<const uint32_t *>(idx), m, n, win, tile_cnt, flag, wend);
-}
-
-// world == 1, pass 2: ordered compaction of the winners (look-up of the
-// earlier tiles' counts), re-zeroing their scratch words.
-template <bool WIRE>
-__device__ __forceinline__ void win_emit1_body(const uint32_t *__restrict__ idx, const float *__restrict__ val,
-                                               size_t m, size_t n, uint32_t ntiles, uint32_t *__restrict__ win,
-                                               const uint32_t *__restrict__ tile_cnt, uint32_t *__restrict__ out_idx,
-                                               float *__restrict__ out_val, uint32_t *out_count, uint32_t flag,
-                                               size_t wend) {
-    __shared__ uint64_t sh64[STG_WAVES];
-    __shared__ uint32_t sh[STG_WAVES + 1];
-    const uint32_t G = gridDim.x, w = blockIdx.x, tid = threadIdx.x;
-    const uint32_t t_begin = (uint32_t)((uint64_t)w * ntiles / G);
-    const uint32_t t_end = (uint32_t)((uint64_t)(w + 1) * ntiles / G);
-    uint64_t tot = 0, bef = 0;
-    for (uint32_t i = tid; i < ntiles; i += STG_WG) {
-        const uint32_t c = tile_cnt[i];
-        tot += c;
-        if (i < t_begin) bef += c;
-    }
-    const uint64_t total = wg_sum64(tot, sh64);
-    uint64_t P = wg_sum64(bef, sh64);
-    for (uint32_t tile = t_begin; tile < t_end; ++tile) {
-        const size_t e = (size_t)tile * MARK_TILE + (size_t)WPER * tid;
-        uint32_t j[WPER];
-        const uint32_t keep = e < m ? win_keep<WIRE>(idx, m, n, win, e, j, flag, wend) : 0u;
-        float v[WPER];  // the values, loaded alongside (clamped addresses)
-        if (WIRE) {
-            if (e < m) wire_val_wp<WPER>(val, flag, wend, m, e, v);
-        } else if (e + WPER <= m && (reinterpret_cast<uintptr_t>(val + e) & 15u) == 0) {
-            const float4 *p = reinterpret_cast<const float4 *>(val + e);
-#pragma unroll
-            for (uint32_t q = 0; q < 4; ++q) {
-                const float4 x = p[q];
-                v[4 * q] = x.x; v[4 * q + 1] = x.y; v[4 * q + 2] = x.z; v[4 * q + 3] = x.w;
-            }
-        } else {
-#pragma unroll
-            for (uint32_t b = 0; b < WPER; ++b) v[b] = m ? val[std::min<size_t>(e + b, m - 1)] : 0.f;
-        }
-        uint32_t tc;
-        uint32_t r = wg_excl_scan((uint32_t)__popc(keep), sh, &tc);
-#pragma unroll
-        for (uint32_t b = 0; b < WPER; ++b) {
-            if (keep >> b & 1u) {
-                out_idx[P + r] = j[b];
-                out_val[P + r] = (0.0f + v[b]) / 1.0f;
-                win[j[b]] = 0;  // scratch back to zero for the next call
-                ++r;
-            }
-        }
-        P += tc;
-    }
-    if (w == 0 && tid == 0) *out_count = (uint32_t)total;
-}
-__global__ void __launch_bounds__(STG_WG) win_emit1(const uint32_t *__restrict__ idx, const float *__restrict__ val,
-                                                    size_t m, size_t n, uint32_t ntiles, uint32_t *__restrict__ win,
-                                                    const uint32_t *__restrict__ tile_cnt,
-                                                    uint32_t *__restrict__ out_idx, float *__restrict__ out_val,
-                                                    uint32_t *out_count) {
-    win_emit1_body<false>(idx, val, m, n, ntiles, win, tile_cnt, out_idx, out_val, out_count, 0u, 0);
-}
-__global__ void __launch_bounds__(STG_WG) win_emit1_w(const void *__restrict__ idx, const void *__restrict__ val,
-                                                      size_t m, size_t n, uint32_t ntiles, uint32_t *__restrict__ win,
-                                                      const uint32_t *__restrict__ tile_cnt,
-                                                      uint32_t *__restrict__ out_idx, float *__restrict__ out_val,
-                                                      uint32_t *out_count, uint32_t flag, size_t wend) {
-    win_emit1_body<true>(static_cast<const uint32_t *>(idx), static_cast<const float *>(val), m, n, ntiles, win,
-                         tile_cnt, out_idx, out_val, out_count, flag, wend);
-}
-
-// world == 1 in one launch after win_mark: tiles in ticket order (a workgroup
-// only waits on tiles taken before its own, so no co-residency is needed);
-// each publishes its winner count as a tagged word, sums the earlier tiles'
-// counts (look-back) and writes its winners at that offset; the last tile
-// writes the count.
 // SGD::optimize_raw on one element (optim/sgd.cpp:34-263, scalar path), with
 // param[id] = x and mom[id] = m loaded by the caller: the same expression as
 // sgd_apply, so a step fused into the emission agrees with it bitwise.
@@ -470,6 +357,11 @@ struct Win1Args {
     AdamLaunch adam;
 };
 
+// world == 1 in one launch after win_mark: tiles in ticket order (a workgroup
+// only waits on tiles taken before its own, so no co-residency is needed);
+// each publishes its winner count as a tagged word, sums the earlier tiles'
+// counts (look-back) and writes its winners at that offset; the last tile
+// writes the count.
 // WP pairs per lane: 4 (the default; 1,024-pair tiles, four times the
 // workgroups and the gathers of 16) or 16 (4,096-pair tiles: 41 workgroups at
 // 167,772 pairs, 13 us per call in the C5 kernel trace).
@@ -903,12 +795,7 @@ hipError_t launch_error_feedback(float *grad, size_t n, const uint32_t *idx, siz
             if (e != hipSuccess) return e;
         }
     }
-    if (numel) {
-        const uint32_t blocks = (uint32_t)std::max<size_t>(1, std::min<size_t>((numel + STG_WG - 1) / STG_WG,
-                                                                              (size_t)num_cu * 4));
-        ef_zero<<<blocks, STG_WG, 0, s>>>(grad, resid, idx, numel, n);
-    }
-    return hipGetLastError();
+    return numel ? launch_ef_zero(grad, resid, idx, numel, n, num_cu, s) : hipGetLastError();
 }
 
 // world > 1, after the ranks' scatters: the marked indices in order.
@@ -924,31 +811,40 @@ static hipError_t launch_mark_emit(size_t n, int world, float *dense, uint8_t *m
     return hipGetLastError();
 }
 
-hipError_t launch_scatter_merge(const uint32_t *idx, const float *val, size_t per_rank, int world, size_t n,
-                                float *dense, uint8_t *mark, uint32_t *out_idx, float *out_val,
-                                uint32_t *out_count, uint32_t *scratch_tiles, uint32_t *win, int num_cu,
-                                hipStream_t s, const Win1Desc &w1) {
-    const uint32_t blocks = (uint32_t)std::max<size_t>(1, std::min<size_t>((per_rank + STG_WG - 1) / STG_WG,
-                                                                          (size_t)num_cu * 8));
+// a flag-0 stream's pointers as the decoded kernels take them (null: no such rank in this launch)
+static const uint32_t *idx32(const RankStream *k) { return k ? static_cast<const uint32_t *>(k->idx) : nullptr; }
+static const float *val32(const RankStream *k) { return k ? static_cast<const float *>(k->val) : nullptr; }
+
+// Every launch takes the decoded kernel when the streams it reads have flag 0
+// (already u32 / f32) and the _w kernel otherwise.
+hipError_t launch_scatter_merge(const RankStream *ranks, size_t per_rank, int world, size_t n, float *dense,
+                                uint8_t *mark, uint32_t *out_idx, float *out_val, uint32_t *out_count,
+                                uint32_t *scratch_tiles, uint32_t *win, int num_cu, hipStream_t s,
+                                const Win1Desc &w1) {
+    const size_t wend = per_rank ? 8 * ((per_rank - 1) / 8) : 0;
     if (world == 1) {
         if (!per_rank) return hipMemsetAsync(out_count, 0, sizeof(uint32_t), s);
-        win_mark<<<blocks, STG_WG, 0, s>>>(idx, per_rank, n, win, w1.desc ? w1.dup : nullptr,
-                                           w1.desc ? w1.ticket : nullptr);
-        const uint32_t nt = (uint32_t)((per_rank + MARK_TILE - 1) / MARK_TILE);
-        if (w1.desc) {  // count and emit in one launch (tagged tile counts, look-back)
-            constexpr uint32_t wp = 4;  // 1,024-pair tiles (2 / 4 / 16 pairs per thread measured no faster)
-            const uint32_t nt1 = (uint32_t)((per_rank + wp * STG_WG - 1) / (wp * STG_WG));
-            Win1Args a{idx, val, per_rank, n, nt1, win, w1.desc, w1.ticket, 0ull /* win_mark zeroed it */, w1.tag,
-                       out_idx, out_val, out_count, w1.fail, w1.dup, w1.sgd != nullptr,
-                       w1.sgd ? *w1.sgd : SgdLaunch{}, w1.adam != nullptr, w1.adam ? *w1.adam : AdamLaunch{}};
-            if (a.fuse_sgd && a.sgd.last) win_emit1t<wp, true><<<nt1, STG_WG, 0, s>>>(a);
+        const RankStream &k = ranks[0];
+        const uint32_t blocks = (uint32_t)std::max<size_t>(1, std::min<size_t>((per_rank + STG_WG - 1) / STG_WG,
+                                                                              (size_t)num_cu * 8));
+        if (k.flag) win_mark_w<<<blocks, STG_WG, 0, s>>>(k.idx, per_rank, n, win, w1.dup, w1.ticket, k.flag, wend);
+        else win_mark<<<blocks, STG_WG, 0, s>>>(idx32(&k), per_rank, n, win, w1.dup, w1.ticket);
+        // count and emit in one launch (tagged tile counts, look-back)
+        constexpr uint32_t wp = 4;  // 1,024-pair tiles (2 / 4 / 16 pairs per thread measured no faster)
+        const uint32_t nt1 = (uint32_t)((per_rank + wp * STG_WG - 1) / (wp * STG_WG));
+        const Win1ArgsW a{{idx32(&k), val32(&k), per_rank, n, nt1, win, w1.desc, w1.ticket,
+                           0ull /* win_mark zeroed it */, w1.tag, out_idx, out_val, out_count, w1.fail, w1.dup,
+                           w1.sgd != nullptr, w1.sgd ? *w1.sgd : SgdLaunch{}, w1.adam != nullptr,
+                           w1.adam ? *w1.adam : AdamLaunch{}},
+                          k.flag, wend};
+        const bool smart = a.fuse_sgd && a.sgd.last;
+        if (k.flag) {
+            if (smart) win_emit1t<wp, true, true><<<nt1, STG_WG, 0, s>>>(a);
+            else win_emit1t<wp, false, true><<<nt1, STG_WG, 0, s>>>(a);
+        } else {  // the decoded kernels take the Win1Args part
+            if (smart) win_emit1t<wp, true><<<nt1, STG_WG, 0, s>>>(a);
             else win_emit1t<wp, false><<<nt1, STG_WG, 0, s>>>(a);
-            if (w1.grid_out) *w1.grid_out = nt1;
-            return hipGetLastError();
         }
-        win_count<<<nt, STG_WG, 0, s>>>(idx, per_rank, n, win, scratch_tiles);
-        const uint32_t G = std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)num_cu, nt));
-        win_emit1<<<G, STG_WG, 0, s>>>(idx, val, per_rank, n, nt, win, scratch_tiles, out_idx, out_val, out_count);
         return hipGetLastError();
     }
     // rank r's scatter beside rank r+1's election (parity halves of `win`,
@@ -957,63 +853,11 @@ hipError_t launch_scatter_merge(const uint32_t *idx, const float *val, size_t pe
         const uint32_t b2 = (uint32_t)std::max<size_t>(1, std::min<size_t>((2 * per_rank + STG_WG - 1) / STG_WG,
                                                                            (size_t)num_cu * 8));
         for (int r = 0; r <= world; ++r) {
-            const bool sc = r >= 1, mk = r < world;
-            const size_t ps = (size_t)(r - 1) * per_rank, pm = (size_t)r * per_rank;
-            scatter_mark<<<b2, STG_WG, 0, s>>>(sc ? idx + ps : nullptr, sc ? val + ps : nullptr,
-                                               win + (size_t)((r - 1) & 1) * n, mk ? idx + pm : nullptr,
-                                               win + (size_t)(r & 1) * n, per_rank, n, dense, mark);
-        }
-    }
-    return launch_mark_emit(n, world, dense, mark, out_idx, out_val, out_count, scratch_tiles, s);
-}
-
-hipError_t launch_scatter_merge_wire(const RankStream *ranks, size_t per_rank, int world, size_t n, float *dense,
-                                     uint8_t *mark, uint32_t *out_idx, float *out_val, uint32_t *out_count,
-                                     uint32_t *scratch_tiles, uint32_t *win, int num_cu, hipStream_t s,
-                                     const Win1Desc &w1) {
-    const size_t wend = per_rank ? 8 * ((per_rank - 1) / 8) : 0;
-    if (world == 1) {
-        const RankStream &k = ranks[0];
-        if (!k.flag)  // already u32 / f32: today's kernels
-            return launch_scatter_merge(static_cast<const uint32_t *>(k.idx), static_cast<const float *>(k.val),
-                                        per_rank, 1, n, dense, mark, out_idx, out_val, out_count, scratch_tiles, win,
-                                        num_cu, s, w1);
-        if (!per_rank) return hipMemsetAsync(out_count, 0, sizeof(uint32_t), s);
-        const uint32_t blocks = (uint32_t)std::max<size_t>(1, std::min<size_t>((per_rank + STG_WG - 1) / STG_WG,
-                                                                              (size_t)num_cu * 8));
-        win_mark_w<<<blocks, STG_WG, 0, s>>>(k.idx, per_rank, n, win, w1.desc ? w1.dup : nullptr,
-                                             w1.desc ? w1.ticket : nullptr, k.flag, wend);
-        if (w1.desc) {
-            constexpr uint32_t wp = 4;
-            const uint32_t nt1 = (uint32_t)((per_rank + wp * STG_WG - 1) / (wp * STG_WG));
-            Win1ArgsW a{{static_cast<const uint32_t *>(k.idx), static_cast<const float *>(k.val), per_rank, n, nt1, win,
-                         w1.desc, w1.ticket, 0ull, w1.tag, out_idx, out_val, out_count, w1.fail, w1.dup,
-                         w1.sgd != nullptr, w1.sgd ? *w1.sgd : SgdLaunch{}, w1.adam != nullptr,
-                         w1.adam ? *w1.adam : AdamLaunch{}},
-                        k.flag, wend};
-            if (a.fuse_sgd && a.sgd.last) win_emit1t<wp, true, true><<<nt1, STG_WG, 0, s>>>(a);
-            else win_emit1t<wp, false, true><<<nt1, STG_WG, 0, s>>>(a);
-            if (w1.grid_out) *w1.grid_out = nt1;
-            return hipGetLastError();
-        }
-        const uint32_t nt = (uint32_t)((per_rank + MARK_TILE - 1) / MARK_TILE);
-        win_count_w<<<nt, STG_WG, 0, s>>>(k.idx, per_rank, n, win, scratch_tiles, k.flag, wend);
-        const uint32_t G = std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)num_cu, nt));
-        win_emit1_w<<<G, STG_WG, 0, s>>>(k.idx, k.val, per_rank, n, nt, win, scratch_tiles, out_idx, out_val,
-                                         out_count, k.flag, wend);
-        return hipGetLastError();
-    }
-    if (per_rank) {
-        const uint32_t b2 = (uint32_t)std::max<size_t>(1, std::min<size_t>((2 * per_rank + STG_WG - 1) / STG_WG,
-                                                                           (size_t)num_cu * 8));
-        for (int r = 0; r <= world; ++r) {
             const RankStream *sc = r >= 1 ? &ranks[r - 1] : nullptr, *mk = r < world ? &ranks[r] : nullptr;
             uint32_t *swin = win + (size_t)((r - 1) & 1) * n, *mwin = win + (size_t)(r & 1) * n;
-            if (!(sc && sc->flag) && !(mk && mk->flag))  // both already u32 / f32
-                scatter_mark<<<b2, STG_WG, 0, s>>>(sc ? static_cast<const uint32_t *>(sc->idx) : nullptr,
-                                                   sc ? static_cast<const float *>(sc->val) : nullptr, swin,
-                                                   mk ? static_cast<const uint32_t *>(mk->idx) : nullptr, mwin,
-                                                   per_rank, n, dense, mark);
+            if (!(sc && sc->flag) && !(mk && mk->flag))
+                scatter_mark<<<b2, STG_WG, 0, s>>>(idx32(sc), val32(sc), swin, idx32(mk), mwin, per_rank, n, dense,
+                                                   mark);
             else
                 scatter_mark_w<<<b2, STG_WG, 0, s>>>(sc ? sc->idx : nullptr, sc ? sc->val : nullptr,
                                                      sc ? sc->flag : 0u, swin, mk ? mk->idx : nullptr,

@@ -1035,86 +1035,104 @@ int stg_error_feedback_device(float *d_grad, size_t n, const uint32_t *d_idx, si
     return STG_OK;
 }
 
-// The streams of one MERGE decompress: decoded pairs back to back (idx, val),
-// or `ranks` -- each rank's stream where it landed, in its wire form.
-struct MergeSrc {
-    const uint32_t *idx;
-    const float *val;
-    const stg_rank_stream_t *ranks;
+// One MERGE decompress call: the rank streams as the launcher takes them, built
+// once at the C entry point, and the entry's other arguments.
+struct MergeCall {
+    std::vector<stg::RankStream> rs;  // `world` streams (none at a wire entry given world < 1 or a null array)
+    bool wire;                        // a wire entry: the streams' flags and buffers are checked
+    size_t per_rank;
+    int world;
+    size_t n;
+    float *dense;
+    uint8_t *mark;
+    uint32_t *out_idx;
+    float *out_val;
+    uint32_t *out_count;
+    void *stream;
 };
 
-static hipError_t launch_merge_src(const MergeSrc &src, size_t per_rank, int world, size_t n, float *dense,
-                                   uint8_t *mark, uint32_t *out_idx, float *out_val, uint32_t *out_count,
-                                   MergeScratch *ms, int ncu, hipStream_t s, const stg::Win1Desc &w1) {
-    if (!src.ranks)
-        return stg::launch_scatter_merge(src.idx, src.val, per_rank, world, n, dense, mark, out_idx, out_val,
-                                         out_count, ms->tiles, ms->win, ncu, s, w1);
-    std::vector<stg::RankStream> rs((size_t)world);
-    for (int r = 0; r < world; ++r) rs[r] = stg::RankStream{src.ranks[r].d_idx, src.ranks[r].d_val,
-                                                            (uint32_t)src.ranks[r].flag};
-    return stg::launch_scatter_merge_wire(rs.data(), per_rank, world, n, dense, mark, out_idx, out_val, out_count,
-                                          ms->tiles, ms->win, ncu, s, w1);
+// decoded pairs back to back: the wire form with flag 0
+static std::vector<stg::RankStream> decoded_streams(const uint32_t *idx, const float *val, size_t per_rank,
+                                                    int world) {
+    std::vector<stg::RankStream> rs((size_t)std::max(world, 0));
+    for (size_t r = 0; r < rs.size(); ++r) rs[r] = stg::RankStream{idx + r * per_rank, val + r * per_rank, 0u};
+    return rs;
 }
 
-// The wire entries' argument checks: all before any device call.
-static int merge_wire_check(const stg_rank_stream_t *ranks, size_t per_rank, int world, const float *d_dense,
-                            const uint8_t *d_mark) {
-    if (world < 1) return fail(STG_ERR_INVALID, "world must be >= 1");
-    if (!ranks) return fail(STG_ERR_INVALID, "null rank stream array");
-    for (int r = 0; r < world; ++r) {
-        if (ranks[r].flag & ~(STG_WIRE_U16_IDX | STG_WIRE_F16_VAL))
-            return fail(STG_ERR_INVALID, "unknown wire flag bits in a rank stream");
-        if (per_rank && (!ranks[r].d_idx || !ranks[r].d_val)) return fail(STG_ERR_INVALID, "null rank stream buffer");
-        // a 16-bit buffer needs its 2-byte alignment, a 32-bit one its 4-byte alignment
-        if ((reinterpret_cast<uintptr_t>(ranks[r].d_idx) & (ranks[r].flag & STG_WIRE_U16_IDX ? 1u : 3u)) ||
-            (reinterpret_cast<uintptr_t>(ranks[r].d_val) & (ranks[r].flag & STG_WIRE_F16_VAL ? 1u : 3u)))
-            return fail(STG_ERR_INVALID, "rank stream buffer misaligned for its element type");
+static std::vector<stg::RankStream> wire_streams(const stg_rank_stream_t *ranks, int world) {
+    std::vector<stg::RankStream> rs(ranks ? (size_t)std::max(world, 0) : 0);
+    for (size_t r = 0; r < rs.size(); ++r)
+        rs[r] = stg::RankStream{ranks[r].d_idx, ranks[r].d_val, (uint32_t)ranks[r].flag};
+    return rs;
+}
+
+// The argument checks of every MERGE entry, none of which needs a device.
+static int merge_check(const MergeCall &c) {
+    if (c.world < 1) return fail(STG_ERR_INVALID, "world must be >= 1");
+    if (c.wire) {
+        if (c.rs.empty()) return fail(STG_ERR_INVALID, "null rank stream array");
+        for (const stg::RankStream &k : c.rs) {
+            if (k.flag & ~(uint32_t)(STG_WIRE_U16_IDX | STG_WIRE_F16_VAL))
+                return fail(STG_ERR_INVALID, "unknown wire flag bits in a rank stream");
+            if (c.per_rank && (!k.idx || !k.val)) return fail(STG_ERR_INVALID, "null rank stream buffer");
+            // a 16-bit buffer needs its 2-byte alignment, a 32-bit one its 4-byte alignment
+            if ((reinterpret_cast<uintptr_t>(k.idx) & (k.flag & STG_WIRE_U16_IDX ? 1u : 3u)) ||
+                (reinterpret_cast<uintptr_t>(k.val) & (k.flag & STG_WIRE_F16_VAL ? 1u : 3u)))
+                return fail(STG_ERR_INVALID, "rank stream buffer misaligned for its element type");
+        }
     }
-    if (world > 1 && (!d_dense || !d_mark)) return fail(STG_ERR_INVALID, "dense/mark scratch required for world > 1");
-    if (world > 1 && (reinterpret_cast<uintptr_t>(d_mark) & 15u)) return fail(STG_ERR_INVALID, "mark scratch must be 16-byte aligned");
+    if (c.world > 1 && (!c.dense || !c.mark)) return fail(STG_ERR_INVALID, "dense/mark scratch required for world > 1");
+    if (c.world > 1 && (reinterpret_cast<uintptr_t>(c.mark) & 15u)) return fail(STG_ERR_INVALID, "mark scratch must be 16-byte aligned");
     return STG_OK;
 }
 
-static int scatter_merge_src(const MergeSrc &src, size_t per_rank, int world, size_t n, float *d_dense,
-                             uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val, uint32_t *d_out_count,
-                             void *stream) {
-    if (world < 1) return fail(STG_ERR_INVALID, "world must be >= 1");
-    if (world > 1 && (!d_dense || !d_mark)) return fail(STG_ERR_INVALID, "dense/mark scratch required for world > 1");
-    if (world > 1 && (reinterpret_cast<uintptr_t>(d_mark) & 15u)) return fail(STG_ERR_INVALID, "mark scratch must be 16-byte aligned");
-    if (n >= (size_t(1) << 32) || per_rank >= (size_t(1) << 32))
+// A checked call on the current device's (device, stream) scratch: look it up,
+// lock, size it, tag the call, launch -- with the optimizer step `sgd` or
+// `adam` (at most one; world 1 only) fused into the emission.
+static int merge_run(const MergeCall &c, const stg::SgdLaunch *sgd = nullptr, const stg::AdamLaunch *adam = nullptr) {
+    if (c.n >= (size_t(1) << 32) || c.per_rank >= (size_t(1) << 32))
         return fail(STG_ERR_UNSUPPORTED, "more than 2^32-1 elements (uint32 indices)");
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     int ncu = 256;
     HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipStream_t s = static_cast<hipStream_t>(c.stream);
     const std::shared_ptr<MergeScratch> ms = merge_scratch(dev, s);
     std::lock_guard<std::mutex> g(ms->mu);
-    int rc = merge_scratch_ensure(ms.get(), s, n, per_rank, world);
+    int rc = merge_scratch_ensure(ms.get(), s, c.n, c.per_rank, c.world);
     if (rc) return rc;
     if (++ms->tag == 0) ms->tag = 1;
-    uint32_t grid = 0;
-    const stg::Win1Desc w1{ms->desc, ms->ticket, 0, ms->tag, &grid, ms->fail,
-                           reinterpret_cast<uint32_t *>(ms->ticket + 1)};
-    HIP_TRY(launch_merge_src(src, per_rank, world, n, d_dense, d_mark, d_out_idx, d_out_val, d_out_count, ms.get(),
-                             ncu, s, w1));
+    const stg::Win1Desc w1{ms->desc, ms->ticket, ms->tag, ms->fail, reinterpret_cast<uint32_t *>(ms->ticket + 1),
+                           sgd, adam};
+    HIP_TRY(stg::launch_scatter_merge(c.rs.data(), c.per_rank, c.world, c.n, c.dense, c.mark, c.out_idx, c.out_val,
+                                      c.out_count, ms->tiles, ms->win, ncu, s, w1));
+    return STG_OK;
+}
+
+static int scatter_merge(const MergeCall &c) {
+    int rc = merge_check(c);
+    return rc ? rc : merge_run(c);
+}
+
+// The fused world-1 step's own limits (per_rank > 0 here).
+static int merge_fused_limits(const MergeCall &c, uint32_t param_len) {
+    if (c.per_rank >= (size_t(1) << 32) || param_len == 0)
+        return fail(STG_ERR_UNSUPPORTED, "more than 2^32-1 elements or an empty parameter");
     return STG_OK;
 }
 
 int stg_scatter_merge_device(const uint32_t *d_idx, const float *d_val, size_t per_rank, int world, size_t n,
                              float *d_dense, uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
                              uint32_t *d_out_count, void *stream) {
-    return scatter_merge_src(MergeSrc{d_idx, d_val, nullptr}, per_rank, world, n, d_dense, d_mark, d_out_idx,
-                             d_out_val, d_out_count, stream);
+    return scatter_merge(MergeCall{decoded_streams(d_idx, d_val, per_rank, world), false, per_rank, world, n, d_dense,
+                                   d_mark, d_out_idx, d_out_val, d_out_count, stream});
 }
 
 int stg_scatter_merge_wire_device(const stg_rank_stream_t *ranks, size_t per_rank, int world, size_t n,
                                   float *d_dense, uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
                                   uint32_t *d_out_count, void *stream) {
-    int rc = merge_wire_check(ranks, per_rank, world, d_dense, d_mark);
-    if (rc) return rc;
-    return scatter_merge_src(MergeSrc{nullptr, nullptr, ranks}, per_rank, world, n, d_dense, d_mark, d_out_idx,
-                             d_out_val, d_out_count, stream);
+    return scatter_merge(MergeCall{wire_streams(ranks, world), true, per_rank, world, n, d_dense, d_mark, d_out_idx,
+                                   d_out_val, d_out_count, stream});
 }
 
 int stg_scatter_merge_check(void *stream) {
@@ -1253,58 +1271,43 @@ int stg_sgd_optimize_raw_device(stg_sgd_t o, const char *name, float *d_param, u
     return STG_OK;
 }
 
-static int merge_optimize_sgd_src(stg_sgd_t o, const char *name, float *d_param, uint32_t param_len,
-                                  const MergeSrc &src, size_t per_rank, int world, float *d_dense, uint8_t *d_mark,
-                                  uint32_t *d_out_idx, float *d_out_val, uint32_t *d_out_count, void *stream) {
+// The MERGE decompress `c` over the parameter (c.n == param_len), then the step
+// on its output -- or, where it can be fused, inside its emission.
+static int merge_optimize_sgd(stg_sgd_t o, const char *name, float *d_param, uint32_t param_len, const MergeCall &c) {
     if (!o || !name) return fail(STG_ERR_INVALID, "null argument");
+    int rc = merge_check(c);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(o->device));
-    if (world != 1 || per_rank == 0) {  // the merge of several ranks, then the step over its output
-        int rc = scatter_merge_src(src, per_rank, world, param_len, d_dense, d_mark, d_out_idx, d_out_val,
-                                   d_out_count, stream);
-        if (rc) return rc;
-        const size_t cap = per_rank * (size_t)world;
-        return stg_sgd_optimize_raw_device(o, name, d_param, param_len, d_out_val, d_out_idx,
-                                           (uint32_t)std::min<size_t>(cap, 0xffffffffu), d_out_count, stream);
+    if (c.world != 1 || c.per_rank == 0) {  // the merge of several ranks, then the step over its output
+        if ((rc = merge_run(c))) return rc;
+        const size_t cap = c.per_rank * (size_t)c.world;
+        return stg_sgd_optimize_raw_device(o, name, d_param, param_len, c.out_val, c.out_idx,
+                                           (uint32_t)std::min<size_t>(cap, 0xffffffffu), c.out_count, c.stream);
     }
     // world 1: the election, then the emission with every winner's step in the
     // same pass (each index is elected once, so the updates commute)
-    if (per_rank >= (size_t(1) << 32) || param_len == 0)
-        return fail(STG_ERR_UNSUPPORTED, "more than 2^32-1 elements or an empty parameter");
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    if ((rc = merge_fused_limits(c, param_len))) return rc;
     stg::SgdLaunch a;
-    int rc = sgd_prepare(o, name, d_param, param_len, s, &a);
-    if (rc) return rc;
-    int ncu = 256;
-    HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, o->device));
-    const std::shared_ptr<MergeScratch> ms = merge_scratch(o->device, s);
-    std::lock_guard<std::mutex> g(ms->mu);
-    if ((rc = merge_scratch_ensure(ms.get(), s, param_len, per_rank, world))) return rc;
-    if (++ms->tag == 0) ms->tag = 1;
-    uint32_t grid = 0;
-    stg::Win1Desc w1{ms->desc, ms->ticket, 0, ms->tag, &grid, ms->fail, reinterpret_cast<uint32_t *>(ms->ticket + 1)};
-    w1.sgd = &a;
-    HIP_TRY(launch_merge_src(src, per_rank, world, param_len, d_dense, d_mark, d_out_idx, d_out_val, d_out_count,
-                             ms.get(), ncu, s, w1));
-    return STG_OK;
+    if ((rc = sgd_prepare(o, name, d_param, param_len, static_cast<hipStream_t>(c.stream), &a))) return rc;
+    return merge_run(c, &a, nullptr);
 }
 
 int stg_merge_optimize_sgd_device(stg_sgd_t o, const char *name, float *d_param, uint32_t param_len,
                                   const uint32_t *d_idx, const float *d_val, size_t per_rank, int world,
                                   float *d_dense, uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
                                   uint32_t *d_out_count, void *stream) {
-    return merge_optimize_sgd_src(o, name, d_param, param_len, MergeSrc{d_idx, d_val, nullptr}, per_rank, world,
-                                  d_dense, d_mark, d_out_idx, d_out_val, d_out_count, stream);
+    return merge_optimize_sgd(o, name, d_param, param_len,
+                              MergeCall{decoded_streams(d_idx, d_val, per_rank, world), false, per_rank, world,
+                                        param_len, d_dense, d_mark, d_out_idx, d_out_val, d_out_count, stream});
 }
 
 int stg_merge_optimize_sgd_wire_device(stg_sgd_t o, const char *name, float *d_param, uint32_t param_len,
                                        const stg_rank_stream_t *ranks, size_t per_rank, int world, float *d_dense,
                                        uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
                                        uint32_t *d_out_count, void *stream) {
-    if (!o || !name) return fail(STG_ERR_INVALID, "null argument");
-    int rc = merge_wire_check(ranks, per_rank, world, d_dense, d_mark);
-    if (rc) return rc;
-    return merge_optimize_sgd_src(o, name, d_param, param_len, MergeSrc{nullptr, nullptr, ranks}, per_rank, world,
-                                  d_dense, d_mark, d_out_idx, d_out_val, d_out_count, stream);
+    return merge_optimize_sgd(o, name, d_param, param_len,
+                              MergeCall{wire_streams(ranks, world), true, per_rank, world, param_len, d_dense, d_mark,
+                                        d_out_idx, d_out_val, d_out_count, stream});
 }
 
 int stg_sgd_get_momentum(stg_sgd_t o, const char *name, float *host_out, uint32_t len, void *stream) {
@@ -1505,57 +1508,42 @@ int stg_adam_optimize_raw_device(stg_adam_t o, const char *name, float *d_param,
     return STG_OK;
 }
 
-static int merge_optimize_adam_src(stg_adam_t o, const char *name, float *d_param, uint32_t param_len,
-                                   const MergeSrc &src, size_t per_rank, int world, float *d_dense, uint8_t *d_mark,
-                                   uint32_t *d_out_idx, float *d_out_val, uint32_t *d_out_count, void *stream) {
+// merge_optimize_sgd's twin: amsgrad is never fused, and caps the step's length.
+static int merge_optimize_adam(stg_adam_t o, const char *name, float *d_param, uint32_t param_len,
+                               const MergeCall &c) {
     if (!o || !name) return fail(STG_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(o->device));
-    if (world != 1 || per_rank == 0 || o->amsgrad) {  // the merge, then the step over its output
-        int rc = scatter_merge_src(src, per_rank, world, param_len, d_dense, d_mark, d_out_idx, d_out_val,
-                                   d_out_count, stream);
-        if (rc) return rc;
-        const size_t cap = std::min<size_t>(per_rank * (size_t)world, o->amsgrad ? param_len : 0xffffffffu);
-        return stg_adam_optimize_raw_device(o, name, d_param, param_len, d_out_val, d_out_idx, (uint32_t)cap,
-                                            d_out_count, stream);
-    }
-    // world 1 without amsgrad: the step inside the emission (see the SGD form)
-    if (per_rank >= (size_t(1) << 32) || param_len == 0)
-        return fail(STG_ERR_UNSUPPORTED, "more than 2^32-1 elements or an empty parameter");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    stg::AdamLaunch a;
-    int rc = adam_prepare(o, name, d_param, param_len, s, &a);
+    int rc = merge_check(c);
     if (rc) return rc;
-    int ncu = 256;
-    HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, o->device));
-    const std::shared_ptr<MergeScratch> ms = merge_scratch(o->device, s);
-    std::lock_guard<std::mutex> g(ms->mu);
-    if ((rc = merge_scratch_ensure(ms.get(), s, param_len, per_rank, world))) return rc;
-    if (++ms->tag == 0) ms->tag = 1;
-    uint32_t grid = 0;
-    stg::Win1Desc w1{ms->desc, ms->ticket, 0, ms->tag, &grid, ms->fail, reinterpret_cast<uint32_t *>(ms->ticket + 1)};
-    w1.adam = &a;
-    HIP_TRY(launch_merge_src(src, per_rank, world, param_len, d_dense, d_mark, d_out_idx, d_out_val, d_out_count,
-                             ms.get(), ncu, s, w1));
-    return STG_OK;
+    HIP_TRY(hipSetDevice(o->device));
+    if (c.world != 1 || c.per_rank == 0 || o->amsgrad) {  // the merge, then the step over its output
+        if ((rc = merge_run(c))) return rc;
+        const size_t cap = std::min<size_t>(c.per_rank * (size_t)c.world, o->amsgrad ? param_len : 0xffffffffu);
+        return stg_adam_optimize_raw_device(o, name, d_param, param_len, c.out_val, c.out_idx, (uint32_t)cap,
+                                            c.out_count, c.stream);
+    }
+    // world 1 without amsgrad: the step inside the emission
+    if ((rc = merge_fused_limits(c, param_len))) return rc;
+    stg::AdamLaunch a;
+    if ((rc = adam_prepare(o, name, d_param, param_len, static_cast<hipStream_t>(c.stream), &a))) return rc;
+    return merge_run(c, nullptr, &a);
 }
 
 int stg_merge_optimize_adam_device(stg_adam_t o, const char *name, float *d_param, uint32_t param_len,
                                    const uint32_t *d_idx, const float *d_val, size_t per_rank, int world,
                                    float *d_dense, uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
                                    uint32_t *d_out_count, void *stream) {
-    return merge_optimize_adam_src(o, name, d_param, param_len, MergeSrc{d_idx, d_val, nullptr}, per_rank, world,
-                                   d_dense, d_mark, d_out_idx, d_out_val, d_out_count, stream);
+    return merge_optimize_adam(o, name, d_param, param_len,
+                               MergeCall{decoded_streams(d_idx, d_val, per_rank, world), false, per_rank, world,
+                                         param_len, d_dense, d_mark, d_out_idx, d_out_val, d_out_count, stream});
 }
 
 int stg_merge_optimize_adam_wire_device(stg_adam_t o, const char *name, float *d_param, uint32_t param_len,
                                         const stg_rank_stream_t *ranks, size_t per_rank, int world, float *d_dense,
                                         uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
                                         uint32_t *d_out_count, void *stream) {
-    if (!o || !name) return fail(STG_ERR_INVALID, "null argument");
-    int rc = merge_wire_check(ranks, per_rank, world, d_dense, d_mark);
-    if (rc) return rc;
-    return merge_optimize_adam_src(o, name, d_param, param_len, MergeSrc{nullptr, nullptr, ranks}, per_rank, world,
-                                   d_dense, d_mark, d_out_idx, d_out_val, d_out_count, stream);
+    return merge_optimize_adam(o, name, d_param, param_len,
+                               MergeCall{wire_streams(ranks, world), true, per_rank, world, param_len, d_dense, d_mark,
+                                         d_out_idx, d_out_val, d_out_count, stream});
 }
 
 int stg_adam_get_state(stg_adam_t o, const char *name, float *host_m, float *host_v, uint32_t len,

@@ -354,35 +354,30 @@ hipError_t launch_radix_level1(const float *a, size_t m, uint32_t last_mask, uin
 hipError_t launch_synth(float *dst, size_t n, uint64_t seed, int dist, uint32_t param, hipStream_t s);
 
 // world == 1 in one launch after the winner election: tagged per-tile counts
-// and a ticket counter of the (device, stream) scratch (desc == nullptr: the
-// two-launch count / emit instead)
+// and a ticket counter of the (device, stream) scratch.  Every merge passes
+// one; desc, ticket, dup and fail are always set (world > 1 reads none of them).
 struct Win1Desc {
     uint64_t *desc;       // per tile {tag:32 | winners:32}, zero at creation
     uint64_t *ticket;     // tile counter, zeroed by each call's win_mark
-    uint64_t base;        // unused (0)
     uint32_t tag;         // call tag >= 1
-    uint32_t *grid_out;   // receives the tiles launched (the ticket advances by it)
     uint32_t *fail;       // sticky failure word of the scratch (a look-back that gave up)
-    uint32_t *dup;        // world 1: set when an index repeats; the ticket then counts from 0 (win_mark zeroes it)
-    const struct SgdLaunch *sgd = nullptr;    // world 1: the SGD step fused into the emission (null: none)
+    uint32_t *dup;        // set when an index repeats; the ticket then counts from 0 (win_mark zeroes it)
+    const struct SgdLaunch *sgd = nullptr;    // the SGD step fused into the emission (null: none)
     const struct AdamLaunch *adam = nullptr;  // ... or the Adam step (no amsgrad)
 };
-hipError_t launch_scatter_merge(const uint32_t *idx, const float *val, size_t per_rank, int world, size_t n,
-                                float *dense, uint8_t *mark, uint32_t *out_idx, float *out_val,
-                                uint32_t *out_count, uint32_t *scratch_tiles, uint32_t *win, int num_cu,
-                                hipStream_t s, const Win1Desc &w1);
 constexpr uint32_t MERGE_TILE = STG_WG * 16;  // pairs / marks per scatter-merge tile
-// The same merge reading each rank's stream where it landed, in the form its
-// flag says it arrived in (STG_WIRE_* bits; wire_dev.h): ranks[r] holds
-// per_rank pairs.  Streams with flag 0 take the decoded kernels.
+// MERGE decompress of `world` rank streams of per_rank pairs each, every one
+// read where it landed, in the form its flag says it arrived in (STG_WIRE_*
+// bits; wire_dev.h).  Flag 0 is the decoded form (u32 / f32) and takes the
+// decoded kernels.
 struct RankStream {
     const void *idx, *val;
     uint32_t flag;
 };
-hipError_t launch_scatter_merge_wire(const RankStream *ranks, size_t per_rank, int world, size_t n, float *dense,
-                                     uint8_t *mark, uint32_t *out_idx, float *out_val, uint32_t *out_count,
-                                     uint32_t *scratch_tiles, uint32_t *win, int num_cu, hipStream_t s,
-                                     const Win1Desc &w1);
+hipError_t launch_scatter_merge(const RankStream *ranks, size_t per_rank, int world, size_t n, float *dense,
+                                uint8_t *mark, uint32_t *out_idx, float *out_val, uint32_t *out_count,
+                                uint32_t *scratch_tiles, uint32_t *win, int num_cu, hipStream_t s,
+                                const Win1Desc &w1);
 
 struct SgdLaunch {
     float *param;

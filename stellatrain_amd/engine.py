@@ -137,19 +137,7 @@ def scatter_merge(idx, val, per_rank: int, world: int, n: int, dense=None, mark=
     accumulate); the output holds each index once (unique1d)."""
     import torch
     dev = idx.device
-    if out_idx is None:
-        out_idx = torch.empty(per_rank * world, dtype=torch.int32, device=dev)
-    if out_val is None:
-        out_val = torch.empty(per_rank * world, dtype=torch.float32, device=dev)
-    if count is None:
-        count = torch.empty(1, dtype=torch.int32, device=dev)
-    if world > 1:
-        if dense is None:
-            dense = torch.zeros(n, dtype=torch.float32, device=dev)
-        if mark is None:
-            mark = torch.zeros(n, dtype=torch.uint8, device=dev)
-    dp = C.c_void_p(dense.data_ptr()) if dense is not None else None
-    mp = C.c_void_p(mark.data_ptr()) if mark is not None else None
+    dp, mp, out_idx, out_val, count = _merge_outputs(dev, n, per_rank, world, dense, mark, out_idx, out_val, count)
     check(lib().stg_scatter_merge_device(C.c_void_p(idx.data_ptr()), C.c_void_p(val.data_ptr()), per_rank, world, n,
                                          dp, mp, C.c_void_p(out_idx.data_ptr()), C.c_void_p(out_val.data_ptr()),
                                          C.c_void_p(count.data_ptr()),
@@ -360,30 +348,22 @@ def scatter_merge_wire(streams, per_rank: int, n: int, dense=None, mark=None, ou
     return out_idx, out_val, count
 
 
-def _merge_optimize_wire(fn, h, param, name, streams, per_rank, dense, mark, out_idx, out_val, count):
-    """``_merge_optimize`` on received streams (``scatter_merge_wire``'s form)."""
+def _merge_optimize(fn, h, param, name, src, per_rank, world, dense, mark, out_idx, out_val, count):
+    """ModuleCpuOptimize::run through one C call (``fn``): the MERGE decompress
+    of ``world`` rank streams into the merged stream (returned), then the
+    optimizer's step on it.  ``src`` is the entry's stream arguments: the
+    decoded (idx, val) pointers, or the one ``_rank_streams`` array."""
     import torch
-    world = len(streams)
-    arr = _rank_streams(streams, per_rank)
     dev, n = param.device, param.numel()
     dp, mp, out_idx, out_val, count = _merge_outputs(dev, n, per_rank, world, dense, mark, out_idx, out_val, count)
-    check(fn(h, name.encode(), C.c_void_p(param.data_ptr()), n, arr, per_rank, world, dp, mp,
+    check(fn(h, name.encode(), C.c_void_p(param.data_ptr()), n, *src, per_rank, world, dp, mp,
              C.c_void_p(out_idx.data_ptr()), C.c_void_p(out_val.data_ptr()), C.c_void_p(count.data_ptr()),
              C.c_void_p(torch.cuda.current_stream(dev.index).cuda_stream)))
     return out_idx, out_val, count
 
 
-def _merge_optimize(fn, h, param, name, idx, val, per_rank, world, dense, mark, out_idx, out_val, count):
-    """ModuleCpuOptimize::run through one C call (``fn``): the MERGE decompress
-    of ``world`` rank streams into the merged stream (returned), then the
-    optimizer's step on it."""
-    import torch
-    dev, n = param.device, param.numel()
-    dp, mp, out_idx, out_val, count = _merge_outputs(dev, n, per_rank, world, dense, mark, out_idx, out_val, count)
-    check(fn(h, name.encode(), C.c_void_p(param.data_ptr()), n, C.c_void_p(idx.data_ptr()), C.c_void_p(val.data_ptr()),
-             per_rank, world, dp, mp, C.c_void_p(out_idx.data_ptr()), C.c_void_p(out_val.data_ptr()),
-             C.c_void_p(count.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev.index).cuda_stream)))
-    return out_idx, out_val, count
+def _decoded(idx, val):
+    return C.c_void_p(idx.data_ptr()), C.c_void_p(val.data_ptr())
 
 
 class SparseSGD:
@@ -458,16 +438,17 @@ class SparseSGD:
         """ModuleCpuOptimize::run (cpu_optimize.cpp:26-100): the MERGE
         decompress, then optimize_raw on its output; at world 1 the step runs
         inside the decompress's emission launch."""
-        return _merge_optimize(lib().stg_merge_optimize_sgd_device, self._h, param, name, idx, val, per_rank, world,
-                               dense, mark, out_idx, out_val, count)
+        return _merge_optimize(lib().stg_merge_optimize_sgd_device, self._h, param, name, _decoded(idx, val), per_rank,
+                               world, dense, mark, out_idx, out_val, count)
 
     def merge_optimize_wire(self, param, name: str, streams, per_rank: int, dense=None, mark=None, out_idx=None,
                             out_val=None, count=None):
         """``merge_optimize`` straight from received streams, one (widx, wval,
         flag) per rank as in ``scatter_merge_wire``; bitwise the result of
         ``wire_decode`` per rank followed by ``merge_optimize``."""
-        return _merge_optimize_wire(lib().stg_merge_optimize_sgd_wire_device, self._h, param, name, streams, per_rank,
-                                    dense, mark, out_idx, out_val, count)
+        return _merge_optimize(lib().stg_merge_optimize_sgd_wire_device, self._h, param, name,
+                               (_rank_streams(streams, per_rank),), per_rank, len(streams), dense, mark, out_idx,
+                               out_val, count)
 
     def momentum_buffer(self, name: str, n: int):
         import torch
@@ -513,15 +494,16 @@ class SparseAdam:
                        out_idx=None, out_val=None, count=None):
         """ModuleCpuOptimize::run with Adam: the step inside the decompress's
         emission at world 1 without amsgrad, else the two calls."""
-        return _merge_optimize(lib().stg_merge_optimize_adam_device, self._h, param, name, idx, val, per_rank, world,
-                               dense, mark, out_idx, out_val, count)
+        return _merge_optimize(lib().stg_merge_optimize_adam_device, self._h, param, name, _decoded(idx, val), per_rank,
+                               world, dense, mark, out_idx, out_val, count)
 
     def merge_optimize_wire(self, param, name: str, streams, per_rank: int, dense=None, mark=None, out_idx=None,
                             out_val=None, count=None):
         """``merge_optimize`` straight from received streams (see
         ``SparseSGD.merge_optimize_wire``)."""
-        return _merge_optimize_wire(lib().stg_merge_optimize_adam_wire_device, self._h, param, name, streams,
-                                    per_rank, dense, mark, out_idx, out_val, count)
+        return _merge_optimize(lib().stg_merge_optimize_adam_wire_device, self._h, param, name,
+                               (_rank_streams(streams, per_rank),), per_rank, len(streams), dense, mark, out_idx,
+                               out_val, count)
 
     def check_device(self) -> None:
         """Raise if a device-side failure was flagged (amsgrad look-back timeout)."""
