@@ -182,7 +182,11 @@ int stg_codec_check(stg_codec_t h);
  * (0xffffffff after a device failure).  Internal scratch is kept per (device,
  * stream) for reuse: 4 B per element of the largest n seen (8 B when world >
  * 1) plus 12 B per 4,096-pair tile -- about 64 MiB for n = 16 Mi at world 1,
- * 128 MiB at world > 1 -- until stg_scatter_merge_release. */
+ * 128 MiB at world > 1 -- until stg_scatter_merge_release.  The batched
+ * stg_merge_optimize_{sgd,adam}_batch_device calls use the same scratch: a
+ * launch of theirs takes 4 B per element of the sum of its tensors' n, a sum
+ * capped at 8 Mi (32 MiB; one larger tensor: its own n), 8 B per 1,024-pair
+ * tile of its tensors, and 6 KiB of per-slot hand-off words. */
 int stg_scatter_merge_device(const uint32_t *d_idx, const float *d_val, size_t per_rank, int world, size_t n,
                              float *d_dense, uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
                              uint32_t *d_out_count, void *stream);
@@ -377,6 +381,62 @@ int stg_merge_optimize_adam_wire_device(stg_adam_t o, const char *name, float *d
                                         const stg_rank_stream_t *ranks, size_t per_rank, int world, float *d_dense,
                                         uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
                                         uint32_t *d_out_count, void *stream);
+
+/* One ModuleCpuOptimize task of a batched call: the arguments of one
+ * stg_merge_optimize_{sgd,adam}_wire_device call (param_len is n; `ranks` is a
+ * host array of `world` entries, flag 0 = decoded u32 / f32). */
+typedef struct stg_merge_task {
+    const char *name;               /* optimizer state name                         */
+    float *d_param;
+    uint32_t param_len;
+    const stg_rank_stream_t *ranks; /* `world` entries                              */
+    size_t per_rank;
+    int world;
+    float *d_dense;                 /* world > 1 only, as stg_scatter_merge_device  */
+    uint8_t *d_mark;
+    uint32_t *d_out_idx;
+    float *d_out_val;
+    uint32_t *d_out_count;
+} stg_merge_task_t;                 /* 88 bytes on LP64; d_dense at offset 48       */
+
+/* The engine's per-iteration ModuleCpuOptimize tasks (one per parameter
+ * tensor, cpu_optimize.cpp:26-106) in one call.  The results -- parameters,
+ * momentum, last-touched words, m / v, every task's merged stream and count,
+ * the SGD handle's iteration count, each name's Adam tick, the failure words
+ * -- are bitwise those of stg_merge_optimize_{sgd,adam}_wire_device on
+ * tasks[0 .. ntasks-1] in order on `stream`.  Task i runs at iteration
+ * iter0 + i (smart momentum sees the factor it would see one by one); the
+ * iterations and ticks of the whole batch are reserved under one hold of the
+ * handle's lock.
+ *   Batched: tasks with world == 1, per_rank > 0 and an optimizer whose step
+ * fuses into the emission (SGD plain and smart, Adam without amsgrad), in the
+ * decoded or any wire form, flags mixed freely.  Up to 16 consecutive such
+ * tasks share one election launch and one emission launch.  A launch also
+ * closes when the sum of its tensors' param_len would pass 8 Mi (32 MiB of
+ * winner words in the (device, stream) scratch of stg_scatter_merge_device; a
+ * larger tensor runs alone on the words a per-tensor call would take), and
+ * before a task whose name already occurs in it, so two tasks on one name run
+ * in order as they would one by one.  Tensors of different names must not
+ * overlap in memory (parameters, streams or outputs): tasks of one launch run
+ * concurrently.
+ *   Not batched: a task with world > 1 or per_rank == 0, and every task of an
+ * Adam handle with amsgrad, runs the per-tensor sequence at its place in the
+ * order.
+ *   All or nothing: every task is checked before any device call or state
+ * change -- a null handle or name, a null `tasks` with ntasks > 0, the
+ * conditions of stg_scatter_merge_wire_device, an empty parameter or 2^32
+ * pairs, a param_len that differs from the name's first call.  A refused call
+ * (STG_ERR_INVALID / STG_ERR_UNSUPPORTED) advances no iteration or tick,
+ * creates no buffer and names the offending task index in stg_last_error().
+ * This covers argument errors only: a HIP failure (STG_ERR_HIP; e.g. an
+ * allocation of a name's state that fails) is found while the tasks are being
+ * prepared or launched, and leaves the tasks before it with their iterations
+ * and ticks taken, as a failing call in the per-tensor sequence would.
+ * ntasks == 0 is STG_OK and does nothing.  A look-back that gives up poisons
+ * its own tensor's count only and sets the scratch's sticky failure word
+ * (stg_scatter_merge_check). */
+int stg_merge_optimize_sgd_batch_device(stg_sgd_t o, const stg_merge_task_t *tasks, size_t ntasks, void *stream);
+int stg_merge_optimize_adam_batch_device(stg_adam_t o, const stg_merge_task_t *tasks, size_t ntasks, void *stream);
 
 /* Synthetic fp32 buckets from the integer-only generator of SURVEY 8(d)
  * (dist 0 = D1, 1 = D2 heavy tail, 2 = D3 zeros with prob param/1e4);

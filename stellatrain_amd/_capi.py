@@ -46,6 +46,14 @@ class StgWireRx(C.Structure):
                 ("d_idx", C.c_void_p), ("d_val", C.c_void_p)]
 
 
+class StgMergeTask(C.Structure):
+    """``stg_merge_task_t``: one ModuleCpuOptimize task of a batched merge_optimize call."""
+    _fields_ = [("name", C.c_char_p), ("d_param", C.c_void_p), ("param_len", C.c_uint32),
+                ("ranks", C.POINTER(StgRankStream)), ("per_rank", C.c_size_t), ("world", C.c_int),
+                ("d_dense", C.c_void_p), ("d_mark", C.c_void_p), ("d_out_idx", C.c_void_p),
+                ("d_out_val", C.c_void_p), ("d_out_count", C.c_void_p)]
+
+
 _lib: C.CDLL | None = None
 
 _SIGS = {
@@ -115,6 +123,8 @@ _SIGS = {
     "stg_merge_optimize_adam_wire_device": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                                       C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "stg_merge_optimize_sgd_batch_device": (C.c_int, [C.c_void_p, C.POINTER(StgMergeTask), C.c_size_t, C.c_void_p]),
+    "stg_merge_optimize_adam_batch_device": (C.c_int, [C.c_void_p, C.POINTER(StgMergeTask), C.c_size_t, C.c_void_p]),
     "stg_synth_fill_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_int, C.c_uint32, C.c_void_p]),
     "stg_last_error": (C.c_char_p, []),
 }

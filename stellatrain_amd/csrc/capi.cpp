@@ -628,6 +628,9 @@ struct MergeScratch {
     uint64_t *desc = nullptr, *ticket = nullptr;
     uint32_t tag = 0;
     uint32_t *fail = nullptr;  // sticky device failure word (a look-back that gave up)
+    // batched launches (merge_batch.hip): a ticket, duplicate flag and failed-launch
+    // tag per tensor slot, zero at creation; they share win, desc, tag and fail
+    stg::MergeSlotCtl *bctl = nullptr;
     ~MergeScratch() {
         (void)hipSetDevice(device);
         (void)hipFree(tiles);
@@ -635,6 +638,7 @@ struct MergeScratch {
         (void)hipFree(desc);
         (void)hipFree(ticket);
         (void)hipFree(fail);
+        (void)hipFree(bctl);
     }
 };
 std::mutex g_merge_mu;
@@ -649,12 +653,13 @@ std::shared_ptr<MergeScratch> merge_scratch(int dev, hipStream_t s) {
     return slot;
 }
 
-// Caller holds m->mu.
-int merge_scratch_ensure(MergeScratch *m, hipStream_t s, size_t n, size_t per_rank, int world) {
+// Caller holds m->mu.  min_tiles: tagged tile counts a batched launch needs
+// (the sum of its tensors' tiles; n is then the sum of their lengths).
+int merge_scratch_ensure(MergeScratch *m, hipStream_t s, size_t n, size_t per_rank, int world, size_t min_tiles = 0) {
     // per-tile counts and their prefixes (the world > 1 mark scan)
     // ... and the world-1 emission's tagged tile counts (tiles of >= MERGE_TILE / 16 pairs)
-    const size_t tiles = std::max(2 * ((std::max(n, per_rank) + stg::MERGE_TILE - 1) / stg::MERGE_TILE) + 2,
-                                  (per_rank + stg::MERGE_TILE / 16 - 1) / (stg::MERGE_TILE / 16) + 2);
+    const size_t tiles = std::max({2 * ((std::max(n, per_rank) + stg::MERGE_TILE - 1) / stg::MERGE_TILE) + 2,
+                                   (per_rank + stg::MERGE_TILE / 16 - 1) / (stg::MERGE_TILE / 16) + 2, min_tiles});
     if (tiles > m->cap_tiles) {
         HIP_TRY(hipStreamSynchronize(s));
         (void)hipFree(m->tiles);
@@ -673,6 +678,10 @@ int merge_scratch_ensure(MergeScratch *m, hipStream_t s, size_t n, size_t per_ra
     if (!m->fail) {  // [0] sticky failure bits, [1] the tag of the last call that failed
         HIP_TRY(hipMalloc(&m->fail, 2 * sizeof(uint32_t)));
         HIP_TRY(hipMemsetAsync(m->fail, 0, 2 * sizeof(uint32_t), s));
+    }
+    if (min_tiles && !m->bctl) {
+        HIP_TRY(hipMalloc(&m->bctl, stg::MERGE_BATCH * sizeof(stg::MergeSlotCtl)));
+        HIP_TRY(hipMemsetAsync(m->bctl, 0, stg::MERGE_BATCH * sizeof(stg::MergeSlotCtl), s));
     }
     const size_t words = std::max<size_t>(world > 1 ? 2 * n : n, 1);  // world > 1: two election halves
     if (words > m->cap_win) {
@@ -1086,20 +1095,19 @@ static int merge_check(const MergeCall &c) {
     return STG_OK;
 }
 
-// A checked call on the current device's (device, stream) scratch: look it up,
-// lock, size it, tag the call, launch -- with the optimizer step `sgd` or
-// `adam` (at most one; world 1 only) fused into the emission.
-static int merge_run(const MergeCall &c, const stg::SgdLaunch *sgd = nullptr, const stg::AdamLaunch *adam = nullptr) {
+// The sizes every launch path can index (uint32 indices and positions).
+static int merge_size_check(const MergeCall &c) {
     if (c.n >= (size_t(1) << 32) || c.per_rank >= (size_t(1) << 32))
         return fail(STG_ERR_UNSUPPORTED, "more than 2^32-1 elements (uint32 indices)");
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    int ncu = 256;
-    HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+    return STG_OK;
+}
+
+// merge_run on a scratch the caller has looked up and locked (ms->mu held; the
+// scratch of the current device and c.stream): size it, tag the call, launch.
+static int merge_run_locked(const MergeCall &c, MergeScratch *ms, int ncu, const stg::SgdLaunch *sgd,
+                            const stg::AdamLaunch *adam) {
     hipStream_t s = static_cast<hipStream_t>(c.stream);
-    const std::shared_ptr<MergeScratch> ms = merge_scratch(dev, s);
-    std::lock_guard<std::mutex> g(ms->mu);
-    int rc = merge_scratch_ensure(ms.get(), s, c.n, c.per_rank, c.world);
+    int rc = merge_scratch_ensure(ms, s, c.n, c.per_rank, c.world);
     if (rc) return rc;
     if (++ms->tag == 0) ms->tag = 1;
     const stg::Win1Desc w1{ms->desc, ms->ticket, ms->tag, ms->fail, reinterpret_cast<uint32_t *>(ms->ticket + 1),
@@ -1107,6 +1115,21 @@ static int merge_run(const MergeCall &c, const stg::SgdLaunch *sgd = nullptr, co
     HIP_TRY(stg::launch_scatter_merge(c.rs.data(), c.per_rank, c.world, c.n, c.dense, c.mark, c.out_idx, c.out_val,
                                       c.out_count, ms->tiles, ms->win, ncu, s, w1));
     return STG_OK;
+}
+
+// A checked call on the current device's (device, stream) scratch: look it up,
+// lock, size it, tag the call, launch -- with the optimizer step `sgd` or
+// `adam` (at most one; world 1 only) fused into the emission.
+static int merge_run(const MergeCall &c, const stg::SgdLaunch *sgd = nullptr, const stg::AdamLaunch *adam = nullptr) {
+    int rc = merge_size_check(c);
+    if (rc) return rc;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    int ncu = 256;
+    HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+    const std::shared_ptr<MergeScratch> ms = merge_scratch(dev, static_cast<hipStream_t>(c.stream));
+    std::lock_guard<std::mutex> g(ms->mu);
+    return merge_run_locked(c, ms.get(), ncu, sgd, adam);
 }
 
 static int scatter_merge(const MergeCall &c) {
@@ -1200,42 +1223,40 @@ int stg_sgd_destroy(stg_sgd_t o) {
 
 // One optimize_raw call's launch arguments (the momentum buffer of `name`,
 // created zeroed on its first call: sgd.cpp:40-47; the iteration count).
-static int sgd_prepare(stg_sgd_t o, const char *name, float *d_param, uint32_t param_len, hipStream_t s,
-                       stg::SgdLaunch *out) {
+// Caller holds o->mu.
+static int sgd_prepare_locked(stg_sgd_t o, const char *name, float *d_param, uint32_t param_len, hipStream_t s,
+                              stg::SgdLaunch *out) {
     bool first = false;
     float *mom = nullptr;
     uint32_t *last = nullptr;
     uint32_t iter;
-    {
-        std::lock_guard<std::mutex> g(o->mu);
-        if (o->smart) {  // the reference's array is zero until the option is on (sgd.cpp:46-47, 258-259)
-            auto it = o->last.find(name);
-            if (it == o->last.end()) {
-                uint32_t *b = nullptr;
-                HIP_TRY(hipMalloc(&b, std::max<size_t>(param_len, 1) * sizeof(uint32_t)));
-                HIP_TRY(hipMemsetAsync(b, 0, std::max<size_t>(param_len, 1) * sizeof(uint32_t), s));
-                it = o->last.emplace(name, std::make_pair(b, param_len)).first;
-            }
-            if (it->second.second != param_len)
-                return fail(STG_ERR_INVALID, "param_len differs from the name's first smart-momentum call");
-            last = it->second.first;
+    if (o->smart) {  // the reference's array is zero until the option is on (sgd.cpp:46-47, 258-259)
+        auto it = o->last.find(name);
+        if (it == o->last.end()) {
+            uint32_t *b = nullptr;
+            HIP_TRY(hipMalloc(&b, std::max<size_t>(param_len, 1) * sizeof(uint32_t)));
+            HIP_TRY(hipMemsetAsync(b, 0, std::max<size_t>(param_len, 1) * sizeof(uint32_t), s));
+            it = o->last.emplace(name, std::make_pair(b, param_len)).first;
         }
-        iter = o->iter;
-        if (o->momentum != 0.f) {
-            auto it = o->mom.find(name);
-            if (it == o->mom.end()) {  // sgd.cpp:40-47: zeroed buffer, first = true
-                float *b = nullptr;
-                HIP_TRY(hipMalloc(&b, std::max<size_t>(param_len, 1) * sizeof(float)));
-                HIP_TRY(hipMemsetAsync(b, 0, std::max<size_t>(param_len, 1) * sizeof(float), s));
-                o->mom.emplace(name, std::make_pair(b, param_len));
-                mom = b;
-                first = true;
-            } else {
-                mom = it->second.first;
-            }
-        }
-        o->iter++;  // sgd.cpp:262
+        if (it->second.second != param_len)
+            return fail(STG_ERR_INVALID, "param_len differs from the name's first smart-momentum call");
+        last = it->second.first;
     }
+    iter = o->iter;
+    if (o->momentum != 0.f) {
+        auto it = o->mom.find(name);
+        if (it == o->mom.end()) {  // sgd.cpp:40-47: zeroed buffer, first = true
+            float *b = nullptr;
+            HIP_TRY(hipMalloc(&b, std::max<size_t>(param_len, 1) * sizeof(float)));
+            HIP_TRY(hipMemsetAsync(b, 0, std::max<size_t>(param_len, 1) * sizeof(float), s));
+            o->mom.emplace(name, std::make_pair(b, param_len));
+            mom = b;
+            first = true;
+        } else {
+            mom = it->second.first;
+        }
+    }
+    o->iter++;  // sgd.cpp:262
     stg::SgdLaunch a{};
     a.param = d_param;
     a.param_len = param_len;
@@ -1253,6 +1274,12 @@ static int sgd_prepare(stg_sgd_t o, const char *name, float *d_param, uint32_t p
     a.fail = o->fail;
     *out = a;
     return STG_OK;
+}
+
+static int sgd_prepare(stg_sgd_t o, const char *name, float *d_param, uint32_t param_len, hipStream_t s,
+                       stg::SgdLaunch *out) {
+    std::lock_guard<std::mutex> g(o->mu);
+    return sgd_prepare_locked(o, name, d_param, param_len, s, out);
 }
 
 int stg_sgd_optimize_raw_device(stg_sgd_t o, const char *name, float *d_param, uint32_t param_len, const float *d_grad,
@@ -1438,40 +1465,38 @@ int stg_adam_destroy(stg_adam_t o) {
 
 // One optimize_raw call's launch arguments: the name's state (created zeroed
 // on its first call: adam.cpp:28-35), its tick and the bias corrections.
-static int adam_prepare(stg_adam_t o, const char *name, float *d_param, uint32_t param_len, hipStream_t s,
-                        stg::AdamLaunch *out) {
+// Caller holds o->mu.
+static int adam_prepare_locked(stg_adam_t o, const char *name, float *d_param, uint32_t param_len, hipStream_t s,
+                               stg::AdamLaunch *out) {
     stg::AdamLaunch a{};
     uint32_t tick;
-    {
-        std::lock_guard<std::mutex> g(o->mu);
-        if (!o->fail) {  // the handle's failure word, allocated with its first state
-            HIP_TRY(hipMalloc(&o->fail, sizeof(uint32_t)));
-            HIP_TRY(hipMemsetAsync(o->fail, 0, sizeof(uint32_t), s));
-        }
-        auto it = o->st.find(name);
-        if (it == o->st.end()) {  // adam.cpp:28-35: zeroed m and v, vmax 0, tick 1
-            stg_adam::Name nm;
-            const size_t L = std::max<size_t>(param_len, 1);
-            // one allocation: m | v | vmax
-            HIP_TRY(hipMalloc(&nm.m, (2 * L + 1) * sizeof(float)));
-            HIP_TRY(hipMemsetAsync(nm.m, 0, (2 * L + 1) * sizeof(float), s));
-            nm.v = nm.m + L;
-            nm.vmax = nm.m + 2 * L;
-            if (o->amsgrad) {  // one tagged uint64 per tile; zero never matches a tick (>= 1)
-                const size_t nt = (L + stg::ADAM_TILE - 1) / stg::ADAM_TILE;
-                HIP_TRY(hipMalloc(&nm.tiles, nt * sizeof(uint64_t)));
-                HIP_TRY(hipMemsetAsync(nm.tiles, 0, nt * sizeof(uint64_t), s));
-            }
-            nm.len = param_len;
-            it = o->st.emplace(name, nm).first;
-        }
-        if (it->second.len != param_len) return fail(STG_ERR_INVALID, "param_len differs from the name's first call");
-        a.m = it->second.m;
-        a.v = it->second.v;
-        a.vmax = it->second.vmax;
-        a.tiles = it->second.tiles;
-        tick = it->second.tick++;  // adam.cpp:40,82
+    if (!o->fail) {  // the handle's failure word, allocated with its first state
+        HIP_TRY(hipMalloc(&o->fail, sizeof(uint32_t)));
+        HIP_TRY(hipMemsetAsync(o->fail, 0, sizeof(uint32_t), s));
     }
+    auto it = o->st.find(name);
+    if (it == o->st.end()) {  // adam.cpp:28-35: zeroed m and v, vmax 0, tick 1
+        stg_adam::Name nm;
+        const size_t L = std::max<size_t>(param_len, 1);
+        // one allocation: m | v | vmax
+        HIP_TRY(hipMalloc(&nm.m, (2 * L + 1) * sizeof(float)));
+        HIP_TRY(hipMemsetAsync(nm.m, 0, (2 * L + 1) * sizeof(float), s));
+        nm.v = nm.m + L;
+        nm.vmax = nm.m + 2 * L;
+        if (o->amsgrad) {  // one tagged uint64 per tile; zero never matches a tick (>= 1)
+            const size_t nt = (L + stg::ADAM_TILE - 1) / stg::ADAM_TILE;
+            HIP_TRY(hipMalloc(&nm.tiles, nt * sizeof(uint64_t)));
+            HIP_TRY(hipMemsetAsync(nm.tiles, 0, nt * sizeof(uint64_t), s));
+        }
+        nm.len = param_len;
+        it = o->st.emplace(name, nm).first;
+    }
+    if (it->second.len != param_len) return fail(STG_ERR_INVALID, "param_len differs from the name's first call");
+    a.m = it->second.m;
+    a.v = it->second.v;
+    a.vmax = it->second.vmax;
+    a.tiles = it->second.tiles;
+    tick = it->second.tick++;  // adam.cpp:40,82
     a.param = d_param;
     a.param_len = param_len;
     a.b1 = o->b1;
@@ -1487,6 +1512,12 @@ static int adam_prepare(stg_adam_t o, const char *name, float *d_param, uint32_t
     a.fail = o->fail;
     *out = a;
     return STG_OK;
+}
+
+static int adam_prepare(stg_adam_t o, const char *name, float *d_param, uint32_t param_len, hipStream_t s,
+                        stg::AdamLaunch *out) {
+    std::lock_guard<std::mutex> g(o->mu);
+    return adam_prepare_locked(o, name, d_param, param_len, s, out);
 }
 
 int stg_adam_optimize_raw_device(stg_adam_t o, const char *name, float *d_param, uint32_t param_len,
@@ -1544,6 +1575,191 @@ int stg_merge_optimize_adam_wire_device(stg_adam_t o, const char *name, float *d
     return merge_optimize_adam(o, name, d_param, param_len,
                                MergeCall{wire_streams(ranks, world), true, per_rank, world, param_len, d_dense, d_mark,
                                          d_out_idx, d_out_val, d_out_count, stream});
+}
+
+// ---- the iteration's ModuleCpuOptimize tasks in one call ----
+// What the two optimizers' batched entries differ in: whether the step fuses,
+// the name's state, and the fields a tensor of a batched launch carries.
+extern "C++" {
+struct SgdBatch {
+    using Handle = stg_sgd_t;
+    using Launch = stg::SgdLaunch;
+    static bool fuses(Handle) { return true; }
+    static bool len_checked(Handle o) { return o->smart; }  // only the last-touched array pins a name's length
+    static int len_check(Handle o, const char *name, uint32_t param_len) {
+        auto it = o->last.find(name);
+        if (it != o->last.end() && it->second.second != param_len)
+            return fail(STG_ERR_INVALID, "param_len differs from the name's first smart-momentum call");
+        return STG_OK;
+    }
+    static int prepare_locked(Handle o, const stg_merge_task_t &t, hipStream_t s, Launch *out) {
+        return sgd_prepare_locked(o, t.name, t.d_param, t.param_len, s, out);
+    }
+    static int opt(const Launch &a) { return a.last ? 1 : 0; }
+    static void common(const Launch &a, stg::MergeBatchArgs &w) { w.sgd = a; }
+    static void fill(const Launch &a, stg::MergeTensor &d) {
+        d.s0 = a.mom;
+        d.s1 = a.last;
+        d.u.sgd.iter = a.iter;
+        d.u.sgd.first = a.first;
+    }
+    // the step over a merge's output (stg_sgd_optimize_raw_device after its prepare)
+    static int step(Handle, Launch a, const MergeCall &c, hipStream_t s) {
+        a.grad = c.out_val;
+        a.gidx = c.out_idx;
+        a.grad_len = (uint32_t)std::min<size_t>(c.per_rank * (size_t)c.world, 0xffffffffu);
+        a.d_grad_len = c.out_count;
+        if (a.grad_len) HIP_TRY(stg::launch_sgd(a, s));
+        return STG_OK;
+    }
+};
+
+struct AdamBatch {
+    using Handle = stg_adam_t;
+    using Launch = stg::AdamLaunch;
+    static bool fuses(Handle o) { return !o->amsgrad; }
+    static bool len_checked(Handle) { return true; }
+    static int len_check(Handle o, const char *name, uint32_t param_len) {
+        auto it = o->st.find(name);
+        if (it != o->st.end() && it->second.len != param_len)
+            return fail(STG_ERR_INVALID, "param_len differs from the name's first call");
+        return STG_OK;
+    }
+    static int prepare_locked(Handle o, const stg_merge_task_t &t, hipStream_t s, Launch *out) {
+        return adam_prepare_locked(o, t.name, t.d_param, t.param_len, s, out);
+    }
+    static int opt(const Launch &) { return 2; }
+    static void common(const Launch &a, stg::MergeBatchArgs &w) { w.adam = a; }
+    static void fill(const Launch &a, stg::MergeTensor &d) {
+        d.s0 = a.m;
+        d.s1 = a.v;
+        d.u.adam.c1 = a.c1;
+        d.u.adam.c2 = a.c2;
+    }
+    static int step(Handle o, Launch a, const MergeCall &c, hipStream_t s) {
+        a.grad = c.out_val;
+        a.gidx = c.out_idx;
+        a.grad_len = (uint32_t)std::min<size_t>(c.per_rank * (size_t)c.world, o->amsgrad ? a.param_len : 0xffffffffu);
+        a.d_grad_len = c.out_count;
+        if (a.grad_len) HIP_TRY(stg::launch_adam(a, s));
+        return STG_OK;
+    }
+};
+
+template <class P>
+static int merge_optimize_batch(typename P::Handle o, const stg_merge_task_t *tasks, size_t ntasks, void *stream) {
+    if (!o) return fail(STG_ERR_INVALID, "null argument");
+    if (!ntasks) return STG_OK;
+    if (!tasks) return fail(STG_ERR_INVALID, "null task array");
+    const auto refuse = [](size_t i, int rc) {
+        g_err = "task " + std::to_string(i) + ": " + g_err;
+        return rc;
+    };
+    // every check of every task, before any device call or state change
+    std::vector<MergeCall> calls;
+    calls.reserve(ntasks);
+    std::vector<uint8_t> fused(ntasks);
+    for (size_t i = 0; i < ntasks; ++i) {
+        const stg_merge_task_t &t = tasks[i];
+        if (!t.name) return refuse(i, fail(STG_ERR_INVALID, "null name"));
+        calls.push_back(MergeCall{wire_streams(t.ranks, t.world), true, t.per_rank, t.world, t.param_len, t.d_dense,
+                                  t.d_mark, t.d_out_idx, t.d_out_val, t.d_out_count, stream});
+        int rc = merge_check(calls[i]);
+        fused[i] = t.world == 1 && t.per_rank > 0 && P::fuses(o);
+        if (!rc && fused[i]) rc = merge_fused_limits(calls[i], t.param_len);
+        if (!rc) rc = merge_size_check(calls[i]);
+        if (rc) return refuse(i, rc);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::vector<typename P::Launch> L(ntasks);
+    {   // the batch's iterations and ticks, contiguous: task i prepares as the i-th call would
+        std::lock_guard<std::mutex> g(o->mu);
+        if (P::len_checked(o)) {
+            std::unordered_map<std::string, uint32_t> seen;
+            for (size_t i = 0; i < ntasks; ++i) {
+                int rc = P::len_check(o, tasks[i].name, tasks[i].param_len);
+                const auto ins = seen.emplace(tasks[i].name, tasks[i].param_len);
+                if (!rc && ins.first->second != tasks[i].param_len)
+                    rc = fail(STG_ERR_INVALID, "param_len differs from an earlier task of the same name");
+                if (rc) return refuse(i, rc);
+            }
+        }
+        HIP_TRY(hipSetDevice(o->device));
+        for (size_t i = 0; i < ntasks; ++i) {
+            const int rc = P::prepare_locked(o, tasks[i], s, &L[i]);
+            if (rc) return refuse(i, rc);  // a HIP failure: the tasks before it keep their iterations
+        }
+    }
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    int ncu = 256;
+    HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+    const std::shared_ptr<MergeScratch> ms = merge_scratch(dev, s);
+    std::lock_guard<std::mutex> g(ms->mu);
+    // the pending launch: tasks [g0, g0 + w.nt), `blocks` tiles and `sum_n` winner words so far
+    stg::MergeBatchArgs w{};
+    size_t g0 = 0, sum_n = 0;
+    uint32_t blocks = 0;
+    const auto flush = [&]() -> int {
+        if (!w.nt) return STG_OK;
+        const int rc = merge_scratch_ensure(ms.get(), s, sum_n, 0, 1, blocks);
+        if (rc) return rc;
+        if (++ms->tag == 0) ms->tag = 1;
+        w.tag = ms->tag;
+        w.win = ms->win;
+        w.desc = ms->desc;
+        w.ctl = ms->bctl;
+        w.fail = ms->fail;
+        HIP_TRY(stg::launch_merge_batch(w, blocks, P::opt(L[g0]), s));
+        w.nt = 0;
+        sum_n = 0;
+        blocks = 0;
+        return STG_OK;
+    };
+    for (size_t i = 0; i < ntasks; ++i) {
+        const stg_merge_task_t &t = tasks[i];
+        int rc;
+        if (!fused[i]) {  // the per-tensor sequence at its place in the order
+            if ((rc = flush())) return rc;
+            if ((rc = merge_run_locked(calls[i], ms.get(), ncu, nullptr, nullptr))) return rc;
+            if ((rc = P::step(o, L[i], calls[i], s))) return rc;
+            continue;
+        }
+        bool close = w.nt == stg::MERGE_BATCH || (w.nt && sum_n + t.param_len > stg::MERGE_BATCH_WIN_CAP);
+        for (size_t q = g0; !close && q < g0 + w.nt; ++q) close = strcmp(tasks[q].name, t.name) == 0;
+        if (close && (rc = flush())) return rc;
+        if (!w.nt) {
+            g0 = i;
+            P::common(L[i], w);
+        }
+        stg::MergeTensor &d = w.t[w.nt++];
+        const stg::RankStream &k = calls[i].rs[0];
+        d.idx = k.idx;
+        d.val = k.val;
+        d.flag = k.flag;
+        d.out_idx = t.d_out_idx;
+        d.out_val = t.d_out_val;
+        d.out_count = t.d_out_count;
+        d.param = t.d_param;
+        d.m = (uint32_t)t.per_rank;
+        d.n = t.param_len;
+        d.blk0 = blocks;
+        d.win0 = (uint32_t)sum_n;
+        d.desc0 = blocks;
+        P::fill(L[i], d);
+        blocks += (uint32_t)((t.per_rank + stg::MERGE_BATCH_TILE - 1) / stg::MERGE_BATCH_TILE);
+        sum_n += t.param_len;
+    }
+    return flush();
+}
+}  // extern "C++"
+
+int stg_merge_optimize_sgd_batch_device(stg_sgd_t o, const stg_merge_task_t *tasks, size_t ntasks, void *stream) {
+    return merge_optimize_batch<SgdBatch>(o, tasks, ntasks, stream);
+}
+
+int stg_merge_optimize_adam_batch_device(stg_adam_t o, const stg_merge_task_t *tasks, size_t ntasks, void *stream) {
+    return merge_optimize_batch<AdamBatch>(o, tasks, ntasks, stream);
 }
 
 int stg_adam_get_state(stg_adam_t o, const char *name, float *host_m, float *host_v, uint32_t len,

@@ -420,6 +420,59 @@ struct AdamLaunch {
 };
 constexpr uint32_t ADAM_TILE = STG_WG * 4;  // amsgrad: elements per workgroup tile
 hipError_t launch_adam(const AdamLaunch &a, hipStream_t s);
+
+// Batched world-1 MERGE decompress + fused optimizer step (merge_batch.hip):
+// one election launch and one emission launch for up to MERGE_BATCH tensors.
+// The table travels by value in the kernel arguments (under 2 KiB of the
+// 4 KiB they may take), so the group is 16 like WireBatch's, not 32.
+constexpr uint32_t MERGE_BATCH = 16;       // tensors per launch pair
+constexpr uint32_t MERGE_BATCH_WP = 4;     // pairs per lane, as the per-tensor emission
+constexpr uint32_t MERGE_BATCH_TILE = MERGE_BATCH_WP * STG_WG;  // pairs per workgroup of either launch
+// winner words (the sum of the tensors' n) one launch may ask of the scratch:
+// 32 MiB.  A launch closes before the sum would pass it; a tensor larger than
+// the cap runs in a launch of its own, on the words a per-tensor call would take.
+constexpr size_t MERGE_BATCH_WIN_CAP = size_t(1) << 23;
+// A tensor slot's hand-off words, each on a 128-byte line of its own.
+struct alignas(128) MergeSlotCtl {
+    uint64_t ticket;     // tiles taken in the ticketed path (zeroed by the election launch)
+    uint32_t pad0[30];
+    uint32_t dup;        // set by the election when an index repeats or is >= n; cleared by the last tile
+    uint32_t pad1[31];
+    uint32_t fail_tag;   // the tag of the last launch in which a look-back of this slot gave up
+    uint32_t pad2[31];
+};
+struct MergeTensor {
+    const void *idx, *val;  // the rank stream where it landed, typed by `flag` (0: u32 / f32)
+    uint32_t *out_idx;
+    float *out_val;
+    uint32_t *out_count;
+    float *param;
+    float *s0;              // SGD: the momentum buffer (null: momentum 0); Adam: m
+    void *s1;               // SGD smart momentum: the last-touched words; Adam: v
+    union {
+        struct { double c1, c2; } adam;          // the name's bias corrections at its tick
+        struct { uint32_t iter, first; } sgd;    // the task's iteration; the name's first call
+    } u;
+    uint32_t m, n;          // pairs; parameter length
+    uint32_t flag;
+    uint32_t blk0;          // first workgroup of this tensor in either launch (as WireBucket::blk0)
+    uint32_t win0, desc0;   // its slices of the scratch: winner words, tagged tile counts
+};
+struct MergeBatchArgs {
+    MergeTensor t[MERGE_BATCH];
+    uint32_t nt;
+    uint32_t tag;           // the launch pair's tag >= 1 on every tile count
+    uint32_t *win;
+    uint64_t *desc;
+    MergeSlotCtl *ctl;      // MERGE_BATCH slots
+    uint32_t *fail;         // the scratch's sticky failure word
+    SgdLaunch sgd;          // the handle-wide scalars (per-tensor fields unset), opt 0 / 1
+    AdamLaunch adam;        // ... opt 2
+};
+static_assert(sizeof(MergeBatchArgs) <= 2048, "kernel arguments: stay well under 4 KiB");
+// opt: 0 = SGD, 1 = SGD with smart momentum, 2 = Adam (no amsgrad); blocks =
+// the sum of the tensors' tiles
+hipError_t launch_merge_batch(const MergeBatchArgs &w, uint32_t blocks, int opt, hipStream_t s);
 hipError_t launch_gather_add(const GatherArgs &a, size_t start, size_t end, int num_cu, hipStream_t s);
 constexpr uint32_t WIRE_BATCH = 16;  // buckets per batched wire launch
 struct WireBucket {

@@ -20,10 +20,10 @@ import ctypes as C
 
 import numpy as np
 
-from ._capi import CodecError, StgRankStream, StgWireRx, check, lib
+from ._capi import CodecError, StgMergeTask, StgRankStream, StgWireRx, check, lib
 from .compressor import Compressor, make_compressor
 
-__all__ = ["CodecEngine", "SparseSGD", "merge_numel", "api_numel", "scatter_merge", "scatter_merge_wire",
+__all__ = ["CodecEngine", "SparseSGD", "MergeTasks", "merge_numel", "api_numel", "scatter_merge", "scatter_merge_wire",
            "wire_decode_batch", "owner_of"]
 
 
@@ -366,6 +366,74 @@ def _decoded(idx, val):
     return C.c_void_p(idx.data_ptr()), C.c_void_p(val.data_ptr())
 
 
+class MergeTasks:
+    """A prebuilt ``stg_merge_task_t`` array: the iteration's ModuleCpuOptimize
+    tasks, marshalled and validated once and reused by every
+    ``merge_optimize_batch`` call on the same tensors (a model's parameters and
+    receive buffers do not move between iterations).  Each item is ``(param,
+    name, streams, per_rank)`` plus, optionally, ``dense, mark, out_idx,
+    out_val, count`` (positional, None to allocate); ``streams`` is a list of
+    (widx, wval, flag) as in ``scatter_merge_wire``, validated as there.
+    ``outputs`` holds one (out_idx, out_val, count) per item: every call on
+    the array writes the same output tensors (and, at world > 1, uses the same
+    dense / mark scratch, left zero by each call), so read an iteration's
+    merged streams before the next call.  The array keeps every tensor it
+    points at alive, the ones allocated here included."""
+
+    def __init__(self, items):
+        import torch
+        items = list(items)
+        self.count = len(items)
+        self.array = (StgMergeTask * max(self.count, 1))()
+        self.outputs = []
+        self.device = items[0][0].device if items else None
+        self._keep = []  # everything the C call reads or writes stays alive with the array
+        dev = self.device
+        for j, it in enumerate(items):
+            if not 4 <= len(it) <= 9:
+                raise ValueError(f"merge_optimize_batch: item {j}: (param, name, streams, per_rank[, dense, mark, "
+                                 "out_idx, out_val, count]) expected")
+            param, name, streams, per_rank = it[:4]
+            dense, mark, out_idx, out_val, count = (tuple(it[4:]) + (None,) * 5)[:5]
+            per_rank = int(per_rank)
+            try:
+                ranks = _rank_streams(streams, per_rank)
+            except ValueError as e:
+                raise ValueError(f"merge_optimize_batch: item {j}: {e}") from None
+            if param.device != dev or streams[0][0].device != dev:
+                raise ValueError(f"merge_optimize_batch: item {j}: tensors on different devices")
+            if param.dtype != torch.float32 or not param.is_contiguous():
+                raise ValueError(f"merge_optimize_batch: item {j}: the parameter must be contiguous float32")
+            world, n = len(streams), param.numel()
+            if world > 1:  # allocated here, not in _merge_outputs: it returns pointers only, and these must outlive it
+                if dense is None:
+                    dense = torch.zeros(n, dtype=torch.float32, device=dev)
+                if mark is None:
+                    mark = torch.zeros(n, dtype=torch.uint8, device=dev)
+            dp, mp, out_idx, out_val, count = _merge_outputs(dev, n, per_rank, world, dense, mark, out_idx, out_val,
+                                                             count)
+            if out_idx.numel() < per_rank * world or out_val.numel() < per_rank * world:
+                raise ValueError(f"merge_optimize_batch: item {j}: output shorter than per_rank * world")
+            nm = name.encode()
+            self.array[j] = StgMergeTask(nm, param.data_ptr(), n, ranks, per_rank, world, dp, mp, out_idx.data_ptr(),
+                                         out_val.data_ptr(), count.data_ptr())
+            self._keep.append((ranks, nm, param, streams, dense, mark))
+            self.outputs.append((out_idx, out_val, count))
+
+
+def _merge_optimize_batch(fn, h, items):
+    """The iteration's ModuleCpuOptimize tasks through one C call (``fn``):
+    ``items`` as ``MergeTasks`` takes them, or a prebuilt ``MergeTasks``."""
+    import torch
+    tasks = items if isinstance(items, MergeTasks) else MergeTasks(items)
+    if not tasks.count:
+        return []
+    rc = fn(h, tasks.array, tasks.count, C.c_void_p(torch.cuda.current_stream(tasks.device.index).cuda_stream))
+    if rc:
+        check(rc)
+    return tasks.outputs
+
+
 class SparseSGD:
     """``SGD`` sparse optimizer (optim/sgd.h:10-50) on the device.  Options as
     SGD::configure (sgd.cpp:265-300); ``optimize_raw`` as sgd.cpp:34-263.
@@ -450,6 +518,16 @@ class SparseSGD:
                                (_rank_streams(streams, per_rank),), per_rank, len(streams), dense, mark, out_idx,
                                out_val, count)
 
+    def merge_optimize_batch(self, items):
+        """``merge_optimize_wire`` on every item in order, in one call: items
+        are ``(param, name, streams, per_rank[, dense, mark, out_idx, out_val,
+        count])``; bitwise the results of the loop.  Consecutive world-1 items
+        (up to 16, parameter lengths summing to at most 8 Mi, distinct names)
+        share one launch pair; world > 1 and empty items run one by one at
+        their place.  ``items`` may be a prebuilt ``MergeTasks`` (no per-call
+        marshalling).  Returns a list of (out_idx, out_val, count)."""
+        return _merge_optimize_batch(lib().stg_merge_optimize_sgd_batch_device, self._h, items)
+
     def momentum_buffer(self, name: str, n: int):
         import torch
         out = np.zeros(n, np.float32)
@@ -504,6 +582,12 @@ class SparseAdam:
         return _merge_optimize(lib().stg_merge_optimize_adam_wire_device, self._h, param, name,
                                (_rank_streams(streams, per_rank),), per_rank, len(streams), dense, mark, out_idx,
                                out_val, count)
+
+    def merge_optimize_batch(self, items):
+        """``merge_optimize_wire`` on every item in order, in one call (see
+        ``SparseSGD.merge_optimize_batch``); with amsgrad every item runs one
+        by one."""
+        return _merge_optimize_batch(lib().stg_merge_optimize_adam_batch_device, self._h, items)
 
     def check_device(self) -> None:
         """Raise if a device-side failure was flagged (amsgrad look-back timeout)."""

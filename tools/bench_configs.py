@@ -19,6 +19,7 @@ times the other configs on one GPU and prints one JSON line per measurement:
       from the codec), and WIRE encode/decode of that stream (u16 idx, fp16 val);
   WMERGE  merge_optimize straight from wire-form rank streams against one
       wire_decode per rank plus the decoded call (60,000 floats and 64 MiB);
+  BMERGE  merge_optimize_batch over 256 tensors against the per-tensor loop;
   E2E thresholdv16 64 MiB host-inclusive (serial and overlapped).
 
 Every device timing rotates over >= 512 MB of distinct buckets so the 256 MB
@@ -610,6 +611,70 @@ def wire_merge(torch, calls):
     return out
 
 
+def batch_merge(torch, repeats=7):
+    """An iteration's ModuleCpuOptimize tasks: merge_optimize_batch (SGD,
+    m = 0.9) against the loop of per-tensor merge_optimize_wire calls it
+    replaces -- same process, same streams and output buffers, a handle each,
+    alternating, `repeats` (>= 5) synchronised sweeps each, the median
+    reported; the batch both marshalled from tensors on every call and from a
+    prebuilt MergeTasks (wall clock: both are host- and launch-bound).  (a) 256 tensors of
+    n = 60,000, k = 600 at wire flag 0 and 1; (b) the first 256 sizes of the C4
+    list at k = 1 %, flag 0.  A tensor's indices are one per stride of n / k,
+    each at a random place in its stride: distinct and sorted."""
+    from stellatrain_amd import MergeTasks, merge_numel, wire_encode
+    from stellatrain_amd.shard import c4_sizes
+    dev = torch.device("cuda", 0)
+    repeats = max(5, repeats)
+    out = []
+    gen = torch.Generator(device="cpu").manual_seed(23)
+    for label, sizes, flag in (("256 tensors n=60000", [60000] * 256, 0), ("256 tensors n=60000", [60000] * 256, 1),
+                               ("first 256 sizes of the C4 list", c4_sizes()[:256], 0)):
+        tasks = []
+        for j, n in enumerate(sizes):
+            k = merge_numel(n, 0.99)
+            stride = n // k
+            idx = (torch.arange(k, dtype=torch.int64) * stride + torch.randint(0, stride, (k,), generator=gen))
+            wi, wv = wire_encode(idx.to(torch.int32).to(dev), torch.randn(k, generator=gen).to(dev), flag)
+            tasks.append((torch.zeros(n, dtype=torch.float32, device=dev), f"{j}@w", [(wi, wv, flag)], k,
+                          torch.empty(k, dtype=torch.int32, device=dev), torch.empty(k, dtype=torch.float32, device=dev),
+                          torch.empty(1, dtype=torch.int32, device=dev)))
+        items = [(p, nm, rs, k, None, None, oi, ov, oc) for p, nm, rs, k, oi, ov, oc in tasks]
+        loop_opt, _ = make_opt("sgd")
+        batch_opt, _ = make_opt("sgd")
+
+        def loop():
+            for p, nm, rs, k, oi, ov, oc in tasks:
+                loop_opt.merge_optimize_wire(p, nm, rs, k, None, None, oi, ov, oc)
+
+        def batch():
+            batch_opt.merge_optimize_batch(items)
+        prebuilt = MergeTasks(items)  # marshalled once, as an engine with fixed tensors would
+
+        def batch_pre():
+            batch_opt.merge_optimize_batch(prebuilt)
+        t = {"loop": [], "batch": [], "pre": []}
+        for r in range(repeats + 2):  # two warm-up rounds (first calls create the state and size the scratch)
+            for name, fn in (("loop", loop), ("batch", batch), ("pre", batch_pre)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                if r >= 2:
+                    t[name].append((time.perf_counter() - t0) * 1e6)
+        union = sum(int(x[6].item()) for x in tasks)  # u16 indices: the saturated repeats merge
+        assert 0 < union <= sum(x[3] for x in tasks)
+        lo, ba, pr = (float(np.median(t[x])) for x in ("loop", "batch", "pre"))
+        out.append({"config": f"BMERGE merge_optimize SGD(m=0.9), {label}, k=1%, wire flag {flag}, world=1",
+                    "tensors": len(sizes), "floats": int(sum(sizes)), "union": union, "repeats": repeats,
+                    "loop_us": round(lo, 1), "batch_us": round(ba, 1), "loop_over_batch": round(lo / ba, 2),
+                    "batch_prebuilt_us": round(pr, 1), "loop_over_prebuilt": round(lo / pr, 2),
+                    "loop_us_min_max": [round(min(t["loop"]), 1), round(max(t["loop"]), 1)],
+                    "batch_us_min_max": [round(min(t["batch"]), 1), round(max(t["batch"]), 1)],
+                    "batch_prebuilt_us_min_max": [round(min(t["pre"]), 1), round(max(t["pre"]), 1)]})
+        del tasks, items, loop_opt, batch_opt
+    return out
+
+
 def cpu_codec(method, mib, ratio, seconds):
     """The reference CPU path beside its GPU row, same run, this host's cores
     (north_star): oracle/_ref/libstg_ref.so (the reference's compress/*.cpp
@@ -680,7 +745,7 @@ def main():
     p.add_argument("--calls", type=int, default=48)
     p.add_argument("--c4-streams", type=int, default=4)
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="per CPU baseline row (0: none)")
-    p.add_argument("--only", default="c2,c3,c4,c5,single,e2e,apply,merge,ef,gather,gfused,wfused,wmerge")
+    p.add_argument("--only", default="c2,c3,c4,c5,single,e2e,apply,merge,ef,gather,gfused,wfused,wmerge,bmerge")
     a = p.parse_args()
     import torch
     from stellatrain_amd import make_compressor
@@ -728,6 +793,9 @@ def main():
             emit(d)
     if "wmerge" in only:
         for d in wire_merge(torch, a.calls):
+            emit(d)
+    if "bmerge" in only:
+        for d in batch_merge(torch):
             emit(d)
 
 

@@ -82,6 +82,7 @@ for s in "$@"; do
         gather) step gather 300 python tools/bench_configs.py --only gather ;;
         gfused) step gfused 300 python tools/bench_configs.py --only gfused,single ;;
         wfused) step wfused 300 python tools/bench_configs.py --only wfused ;;
+        bmerge) step bmerge 300 python tools/bench_configs.py --only bmerge ;;
         tests_wire) step tests_wire 600 python -u -m pytest tests/test_gpu_wire_fused.py tests/test_gpu_wire.py -v -m gpu --timeout 120 --timeout-method thread ;;
         prof_apply) step prof_apply 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$OUT/prof_apply" -o run \
                 -- python3 tools/bench_configs.py --only apply ;;
