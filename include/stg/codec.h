@@ -140,6 +140,62 @@ int stg_merge_gather_compress_device(stg_codec_t h, const stg_bucket_t *bucket, 
 int stg_codec_compress_wire_batch_device(stg_codec_t h, const stg_bucket_t *buckets, const int *flags,
                                          size_t nbuckets, void *stream);
 
+/* One sender-side task of a batched call: one parameter tensor's gather,
+ * compress with error feedback, and wire packing. */
+typedef struct stg_send_task {
+    stg_bucket_t bucket;          /* key; d_src = grad[0] (written); n; k; d_idx / d_val = the WIRE-form
+                                     outputs (idx_cap elements of the types wire_flag selects, val_cap >=
+                                     idx_cap); idx_offset; d_count                                       */
+    float *d_residual;            /* n floats, read by the gather, rewritten by the error feedback;
+                                     NULL = no residual term and no error feedback                      */
+    const float *const *d_grads;  /* host array of num_gpus device pointers, [0] ignored; NULL if
+                                     num_gpus == 1                                                      */
+    int num_gpus;                 /* 1..16; 1 = no gather                                               */
+    int wire_flag;                /* 0..3, STG_WIRE_* bits                                              */
+} stg_send_task_t;                /* 104 bytes on LP64: bucket at 0 (80 bytes; its d_count at 72),
+                                     d_residual at 80, d_grads at 88, num_gpus at 96, wire_flag at 100  */
+
+/* The sender half of a MERGE iteration in one call: ModuleCpuGather::run
+ * (cpu_gather.cpp:59-87), ModuleCompress::run with its error feedback
+ * (compress.cpp:139-186) and queueTx's packing (comm_manager.cpp:486-590) for
+ * every parameter tensor.  The results of task i are bitwise those of this
+ * sequence on temporaries, run on tasks[0 .. ntasks-1] in order on `stream`:
+ *   1. stg_merge_gather_compress_device(h, &b, d_residual, d_grads, num_gpus,
+ *      stream), b being `bucket` with u32 / f32 temporaries of idx_cap slots
+ *      as d_idx / d_val;
+ *   2. stg_wire_encode_device(tmp_idx, tmp_val, count, wire_flag,
+ *      bucket.d_idx, bucket.d_val, stream), count = min(idx_cap, n).
+ * That is: grad[0] gathered and then zeroed at the selected entries; the
+ * residual equal to grad[0] afterwards; the first `count` elements of the
+ * wire-form d_idx / d_val (elements from `count` on are not written);
+ * *d_count; the key's AIMD state.  The zeroing uses the true indices, never
+ * the packed ones (a u16 index at or above 32,768 is saturated on the wire),
+ * which is why error feedback and wire form need this call to be combined.
+ * When idx_cap > count, element 0 is zeroed as well (the reference's
+ * zero-filled unused slots, see stg_error_feedback_device).  A task with
+ * n == 0 writes *d_count = 0 and touches nothing else.
+ *   Launches do not grow with ntasks beyond one per 16 tasks of each kind: the
+ * gather-adds of up to 16 tasks share one launch (a launch also closes before
+ * its grid would pass 8 workgroups per CU; a larger tensor runs alone), then
+ * the thresholdv16 scans run batched (up to 32 buckets per launch, residual
+ * copy fused) into u32 / f32 staging of the stream's workspace, then one
+ * launch per 16 tasks copies the ragged tails, zeroes the selected entries
+ * and writes the wire form.  A single task of 2^22..2^24 elements keeps the
+ * one-bucket scan with the sources summed inside its streaming pass.  Staging
+ * takes 8 bytes per idx_cap slot of the call, kept with the workspace.
+ *   thresholdv16 only (STG_ERR_UNSUPPORTED for the other codecs).
+ *   All or nothing: every task is checked before any device call or key-state
+ * change, and stg_last_error() names the offending task index.
+ * STG_ERR_INVALID: a null handle, a null `tasks` with ntasks > 0, the
+ * conditions of stg_codec_compress_device (val_cap < idx_cap, a null d_count),
+ * wire_flag bits outside 0..3, num_gpus outside 1..16, with n > 0 a null
+ * bucket buffer, a null d_grads at num_gpus > 1 or a null source, and a key
+ * that occurs twice in the call (the engine has one task per key per
+ * iteration; the scans of a call all precede its finishing launches).
+ * ntasks == 0 is STG_OK.  Buffers of different tasks must not overlap: the
+ * tasks of one launch run concurrently.  Async on `stream`. */
+int stg_merge_send_batch_device(stg_codec_t h, const stg_send_task_t *tasks, size_t ntasks, void *stream);
+
 /* Per-key AIMD state (thresholdv16.cpp:243-259, thresholdv.cpp:72-80), read
  * back for parity tests; synchronises `stream`.  Returns STG_ERR_INVALID when
  * the key has never been compressed.  For threshold-v pass the src pointer

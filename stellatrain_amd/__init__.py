@@ -5,9 +5,9 @@ thresholdv16 / threshold-v / Top-k codecs, the MERGE decompress and the
 sparse SGD apply, as hand-written HIP kernels for gfx950 behind the C-ABI in
 include/stg/codec.h.  See DESIGN.md.
 """
-from ._capi import CodecError, StgMergeTask, lib  # noqa: F401
-from .compressor import (Compressor, ThresholdvCompressor, ThresholdvCompressor16, TopkCompressor,  # noqa: F401
-                         make_compressor)
+from ._capi import CodecError, StgMergeTask, StgSendTask, lib  # noqa: F401
+from .compressor import (Compressor, SendTasks, ThresholdvCompressor, ThresholdvCompressor16,  # noqa: F401
+                         TopkCompressor, make_compressor)
 from .engine import (CodecEngine, MergeTasks, SparseAdam, SparseSGD, api_numel, merge_numel, owner_of,  # noqa: F401
                      gather_add, gather_slice, scatter_merge, scatter_merge_wire, wire_decode, wire_decode_batch,
                      wire_encode, wire_encode_batch, wire_flag)

@@ -54,6 +54,12 @@ class StgMergeTask(C.Structure):
                 ("d_out_val", C.c_void_p), ("d_out_count", C.c_void_p)]
 
 
+class StgSendTask(C.Structure):
+    """``stg_send_task_t``: one sender-side task of ``stg_merge_send_batch_device``."""
+    _fields_ = [("bucket", StgBucket), ("d_residual", C.c_void_p), ("d_grads", C.POINTER(C.c_void_p)),
+                ("num_gpus", C.c_int), ("wire_flag", C.c_int)]
+
+
 _lib: C.CDLL | None = None
 
 _SIGS = {
@@ -105,6 +111,7 @@ _SIGS = {
                                                        C.c_void_p]),
     "stg_merge_gather_compress_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                    C.c_void_p]),
+    "stg_merge_send_batch_device": (C.c_int, [C.c_void_p, C.POINTER(StgSendTask), C.c_size_t, C.c_void_p]),
     "stg_gather_slice": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "stg_gather_add_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int,
                                         C.c_void_p]),

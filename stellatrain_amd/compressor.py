@@ -25,9 +25,9 @@ import ctypes as C
 
 import numpy as np
 
-from ._capi import CodecError, StgBucket, check, lib
+from ._capi import CodecError, StgBucket, StgSendTask, check, lib
 
-__all__ = ["Compressor", "ThresholdvCompressor16", "ThresholdvCompressor", "TopkCompressor", "make_compressor",
+__all__ = ["Compressor", "SendTasks", "ThresholdvCompressor16", "ThresholdvCompressor", "TopkCompressor", "make_compressor",
            "CodecError"]
 
 
@@ -38,6 +38,66 @@ def _is_torch(x) -> bool:
 def _stream_ptr(device: int) -> int:
     import torch
     return torch.cuda.current_stream(device).cuda_stream
+
+
+class SendTasks:
+    """A prebuilt ``stg_send_task_t`` array: the iteration's sender-side tasks,
+    marshalled and validated once and reused by every
+    ``Compressor.merge_send_batch_async`` call on the same tensors (a model's
+    gradient, residual and send buffers do not move between iterations).  Each
+    item is ``(key, grads, k, dst_idx, dst_val, residual, wire_flag[,
+    idx_offset])``: ``grads[0]`` is the bucket, ``residual`` may be None, the
+    dst dtypes follow the flag (int16 / int32 indices, int16 / float32 values).
+    ``counts`` (int32, one per item) receives the pair counts of every call on
+    the array.  The array keeps every tensor it points at alive."""
+
+    def __init__(self, items, counts=None):
+        import torch
+        items = list(items)
+        self.count = len(items)
+        self.array = (StgSendTask * max(self.count, 1))()
+        self.device = items[0][1][0].device if items and len(items[0]) > 1 and len(items[0][1]) else None
+        self.counts = counts
+        self._keep = []
+        if not items:
+            return
+        dev = self.device
+        if self.counts is None:
+            self.counts = torch.zeros(self.count, dtype=torch.int32, device=dev)
+        if self.counts.numel() < self.count or self.counts.dtype != torch.int32 or not self.counts.is_contiguous():
+            raise ValueError("merge_send_batch: counts must be a contiguous int32 tensor, one element per item")
+        for j, it in enumerate(items):
+            if not 7 <= len(it) <= 8:
+                raise ValueError(f"merge_send_batch: item {j}: (key, grads, k, dst_idx, dst_val, residual, wire_flag"
+                                 "[, idx_offset]) expected")
+            key, grads, k, di, dv, resid, flag = it[:7]
+            off = int(it[7]) if len(it) > 7 else 0
+            flag = int(flag)
+            grads = list(grads)
+            if flag not in (0, 1, 2, 3):
+                raise ValueError(f"merge_send_batch: item {j}: wire flag {flag!r} outside 0..3")
+            if not 1 <= len(grads) <= 16:
+                raise ValueError(f"merge_send_batch: item {j}: 1..16 gradient tensors expected")
+            want = (torch.int16 if flag & 1 else torch.int32, torch.int16 if flag & 2 else torch.float32)
+            if (di.dtype, dv.dtype) != want:
+                raise ValueError(f"merge_send_batch: item {j}: dtypes {di.dtype}/{dv.dtype} do not match wire flag {flag}")
+            if dv.numel() < di.numel():
+                raise ValueError(f"merge_send_batch: item {j}: dst_val shorter than dst_idx")
+            n = grads[0].numel()
+            srcs = grads + ([resid] if resid is not None else [])
+            if any(t.numel() != n or t.dtype != torch.float32 for t in srcs):
+                raise ValueError(f"merge_send_batch: item {j}: float32 gradients and residual of one size")
+            if not all(t.is_contiguous() for t in srcs + [di, dv]):
+                raise ValueError(f"merge_send_batch: item {j}: tensors must be contiguous")
+            if not all(t.is_cuda and t.device == dev for t in srcs + [di, dv, self.counts]):
+                raise ValueError(f"merge_send_batch: item {j}: tensors must be on one HIP device")
+            kb = key.encode()
+            ptrs = (C.c_void_p * len(grads))(*[t.data_ptr() for t in grads])
+            b = StgBucket(kb, grads[0].data_ptr(), n, int(k), di.data_ptr(), di.numel(), dv.data_ptr(), dv.numel(),
+                          off, self.counts.data_ptr() + 4 * j)
+            self.array[j] = StgSendTask(b, resid.data_ptr() if resid is not None else None,
+                                        ptrs if len(grads) > 1 else None, len(grads), flag)
+            self._keep.append((kb, ptrs, grads, di, dv, resid))
 
 
 class Compressor:
@@ -181,6 +241,33 @@ class Compressor:
             self._h, C.byref(b), C.c_void_p(residual.data_ptr()) if residual is not None else None, ptrs,
             len(grads), C.c_void_p(sp)))
         return count
+
+    def merge_send_batch_async(self, items, stream=None, counts=None):
+        """The sender half of a MERGE iteration in one call
+        (``stg_merge_send_batch_device``): for every item ``(key, grads, k,
+        dst_idx, dst_val, residual, wire_flag[, idx_offset])`` the gather-add
+        ``grads[0] += residual + grads[1] + ... + grads[N-1]``, the compress of
+        ``grads[0]`` under ``key`` with its error feedback (``residual`` not
+        None: the selected entries zeroed by their true indices, the residual
+        left equal to the bucket) and the stream written in its wire form --
+        bitwise ``merge_gather_compress_async`` into u32 / f32 temporaries
+        followed by ``wire_encode`` of the count = min(dst_idx.numel(), n)
+        pairs.  ``dst_idx`` is int16 under flag 1 (else int32), ``dst_val``
+        int16-typed fp16 bits under flag 2 (else float32); ``dst_idx.numel()``
+        is the pair capacity.  Keys must be distinct within a call.
+        thresholdv16 only.  ``items`` may be a prebuilt ``SendTasks``.  Returns
+        the int32 counts tensor (no host sync)."""
+        tasks = items if isinstance(items, SendTasks) else SendTasks(items, counts=counts)
+        if not tasks.count:
+            return tasks.counts
+        sp = stream if stream is not None else _stream_ptr(tasks.device.index)
+        f = getattr(self, "_fn_send_cache", None)
+        if f is None:
+            f = self._fn_send_cache = lib().stg_merge_send_batch_device
+        rc = f(self._h, tasks.array, tasks.count, C.c_void_p(sp))
+        if rc:
+            check(rc)
+        return tasks.counts
 
     @staticmethod
     def bucket_array(rows):

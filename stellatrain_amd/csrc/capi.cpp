@@ -491,9 +491,9 @@ int launch_tv16_group(stg_codec *h, Workspace *ws, std::vector<stg::Tv16Bucket> 
 
 // thresholdv16 over a sequence of buckets: runs of distinct keys (<= 16)
 // share one launch; the per-key state makes a repeated key wait for the
-// launch that updates it.
+// launch that updates it.  `gather` (if any) belongs to bucket gather_at.
 int run_tv16(stg_codec *h, const stg_bucket_t *bk, size_t nbk, hipStream_t s, float *const *resid = nullptr,
-             const stg::GatherArgs *gather = nullptr, const int *wire_flags = nullptr) {
+             const stg::GatherArgs *gather = nullptr, const int *wire_flags = nullptr, size_t gather_at = 0) {
     HIP_TRY(hipSetDevice(h->device));
     Workspace *ws = nullptr;
     int rc = h->workspace(s, &ws);
@@ -526,7 +526,7 @@ int run_tv16(stg_codec *h, const stg_bucket_t *bk, size_t nbk, hipStream_t s, fl
         t.state = st;
         t.first = fresh;
         t.resid = resid ? resid[i] : nullptr;
-        t.gather = i == 0 ? gather : nullptr;
+        t.gather = i == gather_at ? gather : nullptr;
         t.wflag = wire_flags ? (uint32_t)wire_flags[i] & 3u : 0u;
         grp.push_back(t);
     }
@@ -895,6 +895,165 @@ int stg_merge_gather_compress_device(stg_codec_t h, const stg_bucket_t *bucket, 
     if (d_residual) return stg_merge_compress_batch_device(h, &b, &d_residual, 1, stream);
     return run_device(h, b.key, b.d_src, b.d_src, b.n, b.k, b.d_idx, b.idx_cap, b.d_val, b.val_cap, b.idx_offset,
                       b.d_count, s);
+}
+
+// the layout include/stg/codec.h documents (and stellatrain_amd/_capi.py mirrors)
+static_assert(sizeof(stg_bucket_t) == 80 && offsetof(stg_bucket_t, d_count) == 72, "stg_bucket_t layout");
+static_assert(sizeof(stg_send_task_t) == 104 && offsetof(stg_send_task_t, d_residual) == 80 &&
+                  offsetof(stg_send_task_t, d_grads) == 88 && offsetof(stg_send_task_t, num_gpus) == 96 &&
+                  offsetof(stg_send_task_t, wire_flag) == 100,
+              "stg_send_task_t layout");
+
+int stg_merge_send_batch_device(stg_codec_t h, const stg_send_task_t *tasks, size_t ntasks, void *stream) {
+    CritPath crit_path;
+    if (!h) return fail(STG_ERR_INVALID, "null codec handle");
+    if (ntasks && !tasks) return fail(STG_ERR_INVALID, "null task array");
+    if (h->method != M_TV16)
+        return fail(STG_ERR_UNSUPPORTED, "the one-call send path scans with thresholdv16 only "
+                                         "(gather-compress, then stg_wire_encode_device)");
+    // all or nothing: every task is checked before any device call or key state exists
+    auto tfail = [](size_t i, int code, const std::string &msg) {
+        return fail(code, "task " + std::to_string(i) + ": " + msg);
+    };
+    std::unordered_map<std::string, size_t> seen;
+    size_t live = 0, one = 0;  // tasks with n > 0; the last of them
+    for (size_t i = 0; i < ntasks; ++i) {
+        const stg_send_task_t &t = tasks[i];
+        const stg_bucket_t &b = t.bucket;
+        const int rc = validate(h, b.n, b.k, b.idx_cap, b.val_cap, b.d_count);
+        if (rc) return tfail(i, rc, std::string(g_err));
+        if (t.wire_flag & ~3) return tfail(i, STG_ERR_INVALID, "unknown wire flag bits");
+        if (t.num_gpus < 1 || t.num_gpus > (int)stg::GATHER_MAX)
+            return tfail(i, STG_ERR_INVALID, "num_gpus must be in [1, 16]");
+        if (b.n) {
+            if (!b.d_src || (b.idx_cap && (!b.d_idx || !b.d_val))) return tfail(i, STG_ERR_INVALID, "null bucket buffer");
+            if (t.num_gpus > 1 && !t.d_grads) return tfail(i, STG_ERR_INVALID, "null d_grads");
+            for (int r = 1; r < t.num_gpus; ++r)
+                if (!t.d_grads[r]) return tfail(i, STG_ERR_INVALID, "null source");
+            ++live;
+            one = i;
+        }
+        const auto ins = seen.emplace(state_key(h->method, b.key, b.d_src), i);
+        if (!ins.second)
+            return tfail(i, STG_ERR_INVALID, "key repeats task " + std::to_string(ins.first->second) +
+                                                 "'s (one task per key per call)");
+    }
+    if (!ntasks) return STG_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(h->device));
+    Workspace *ws = nullptr;
+    int rc = h->workspace(s, &ws);
+    if (rc) return rc;
+    // The scans write u32 / f32 pairs into staging, sized before the first
+    // launch and held for the whole call: it never moves between a task's scan
+    // and its finish.  Slices start on 256 bytes (the emission stores 16 bytes).
+    std::lock_guard<std::mutex> wg(ws->wire_mu);
+    auto slice = [](size_t cap) { return (cap + 63) / 64 * 64; };
+    size_t total = 0;
+    for (size_t i = 0; i < ntasks; ++i)
+        if (tasks[i].bucket.n) total += slice(tasks[i].bucket.idx_cap);
+    if ((rc = ws->ensure_wire_stage(std::max<size_t>(total, 1)))) return rc;
+    std::vector<stg_bucket_t> bk(ntasks);
+    std::vector<float *> res(ntasks);
+    size_t off = 0;
+    for (size_t i = 0; i < ntasks; ++i) {
+        bk[i] = tasks[i].bucket;
+        res[i] = tasks[i].d_residual;
+        if (!bk[i].n) continue;  // (run_tv16 writes its zero count)
+        bk[i].d_idx = ws->wst_pos + off;
+        bk[i].d_val = ws->wst_val + off;
+        bk[i].val_cap = bk[i].idx_cap;
+        off += slice(bk[i].idx_cap);
+    }
+    auto gather_of = [&](size_t i) {
+        const stg_send_task_t &t = tasks[i];
+        stg::GatherArgs g{};
+        g.dst = const_cast<float *>(t.bucket.d_src);
+        g.resid = t.d_residual;
+        g.nsrc = (uint32_t)t.num_gpus;
+        for (int r = 1; r < t.num_gpus; ++r) g.src[r] = t.d_grads[r];
+        return g;
+    };
+    // One task of 16-64 MiB alone: the one-bucket scan sums the sources in its
+    // own streaming pass (tv16lone.hip), one pass over the bucket instead of two.
+    const bool lone = live == 1 && tasks[one].bucket.n >= (size_t(1) << 22) && tasks[one].bucket.n <= (size_t(1) << 24);
+    if (lone) {
+        const stg::GatherArgs g = gather_of(one);
+        if ((rc = run_tv16(h, bk.data(), ntasks, s, res.data(), &g, nullptr, one))) return rc;
+    } else {
+        // gather groups: a launch closes at SEND_BATCH tasks or before its grid
+        // would pass num_cu * 8 workgroups (a larger tensor runs alone)
+        stg::SendGatherBatch gb{};
+        uint64_t blocks = 0;
+        const uint64_t cap = (uint64_t)h->num_cu * 8;
+        auto flush = [&]() -> int {
+            if (gb.nt) HIP_TRY(stg::launch_gather_add_batch(gb, (uint32_t)blocks, s));
+            gb = stg::SendGatherBatch{};
+            blocks = 0;
+            return STG_OK;
+        };
+        for (size_t i = 0; i < ntasks; ++i) {
+            const stg_send_task_t &t = tasks[i];
+            const size_t n = t.bucket.n;
+            if (!n || (!t.d_residual && t.num_gpus <= 1)) continue;  // (no term to add)
+            const stg::GatherArgs g = gather_of(i);
+            auto phase = [](const float *p) { return reinterpret_cast<uintptr_t>(p) & 15u; };
+            const uintptr_t ph = phase(g.dst);
+            bool vec = (ph & 3u) == 0;
+            if (g.resid) vec &= phase(g.resid) == ph;
+            for (uint32_t r = 1; r < g.nsrc; ++r) vec &= phase(g.src[r]) == ph;
+            const size_t head = vec ? std::min<size_t>(n, ((16u - ph) & 15u) / 4u) : 0;
+            const uint64_t nbk = vec ? std::max<uint64_t>(1, ((n - head) / 4 + stg::SEND_GATHER_TILE / 4 - 1) /
+                                                                 (stg::SEND_GATHER_TILE / 4))
+                                     : (n + stg::SEND_GATHER_TILE - 1) / stg::SEND_GATHER_TILE;
+            if (gb.nt == stg::SEND_BATCH || (gb.nt && blocks + nbk > cap))
+                if ((rc = flush())) return rc;
+            stg::SendGather &d = gb.t[gb.nt++];
+            d.dst = g.dst;
+            d.resid = g.resid;
+            for (uint32_t r = 1; r < g.nsrc; ++r) d.src[r] = g.src[r];
+            d.n = n;
+            d.nsrc = g.nsrc;
+            d.blk0 = (uint32_t)blocks;
+            d.vec = vec;
+            d.head = (uint32_t)head;
+            blocks += nbk;
+        }
+        if ((rc = flush())) return rc;
+        if ((rc = run_tv16(h, bk.data(), ntasks, s, res.data()))) return rc;
+    }
+    // finish groups: tail copy, error feedback by the true indices, wire form
+    stg::SendFinishBatch fb{};
+    uint64_t blocks = 0;
+    auto flush = [&]() -> int {
+        if (fb.nt) HIP_TRY(stg::launch_ef_pack_batch(fb, (uint32_t)blocks, s));
+        fb = stg::SendFinishBatch{};
+        blocks = 0;
+        return STG_OK;
+    };
+    for (size_t i = 0; i < ntasks; ++i) {
+        const stg_bucket_t &b = tasks[i].bucket;
+        if (!b.n) continue;
+        const size_t count = std::min<size_t>(b.idx_cap, b.n);  // the pairs the fill writes
+        if (!count && !tasks[i].d_residual) continue;
+        const uint64_t nbk = std::max<uint64_t>(1, (count + STG_WG - 1) / STG_WG);
+        if (fb.nt == stg::SEND_BATCH || blocks + nbk > 0x7fffffffull)
+            if ((rc = flush())) return rc;
+        stg::SendFinish &d = fb.t[fb.nt++];
+        d.idx = bk[i].d_idx;
+        d.val = bk[i].d_val;
+        d.idx_out = b.d_idx;
+        d.val_out = b.d_val;
+        d.grad = const_cast<float *>(b.d_src);
+        d.resid = tasks[i].d_residual;
+        d.n = b.n;
+        d.count = (uint32_t)count;
+        d.flag = (uint32_t)tasks[i].wire_flag;
+        d.blk0 = (uint32_t)blocks;
+        d.zero0 = b.idx_cap > count;
+        blocks += nbk;
+    }
+    return flush();
 }
 
 int stg_codec_compress_host(stg_codec_t h, const char *key, const float *src, size_t n, uint32_t k,

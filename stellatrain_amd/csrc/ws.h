@@ -487,6 +487,44 @@ struct WireBatch {
     uint32_t nb;
 };
 hipError_t launch_wire_encode_batch(const WireBatch &w, uint32_t blocks, hipStream_t s);
+// The one-call MERGE send path (send_batch.hip): the gather-add before the
+// scans and the error feedback + wire packing after them, each for up to
+// SEND_BATCH tensors per launch.  The tables travel by value in the kernel
+// arguments, workgroups dealt by blk0 as above.
+constexpr uint32_t SEND_BATCH = 16;                   // tensors per launch of either kernel
+constexpr uint32_t SEND_GATHER_TILE = STG_WG * 16;    // elements per gather workgroup (four float4 per lane)
+struct SendGather {
+    float *dst;                    // grad[0]
+    const float *resid;            // residual term (or null)
+    const float *src[GATHER_MAX];  // src[1 .. nsrc-1] = grad[1 .. N-1]; src[0] unused
+    uint64_t n;
+    uint32_t nsrc;                 // N
+    uint32_t blk0;                 // first workgroup of this tensor in the launch
+    uint32_t vec;                  // every pointer shares one 16-byte phase: float4 body
+    uint32_t head;                 // vec: elements before the first 16-byte aligned one (< 4, <= n)
+};
+struct SendGatherBatch {
+    SendGather t[SEND_BATCH];
+    uint32_t nt;
+};
+static_assert(sizeof(SendGatherBatch) <= 3072, "kernel arguments: stay under 4 KiB");
+hipError_t launch_gather_add_batch(const SendGatherBatch &w, uint32_t blocks, hipStream_t s);
+struct SendFinish {
+    const uint32_t *idx;           // the scan's staged pairs: true indices (+ idx_offset) ...
+    const float *val;              // ... and values, `count` of each
+    void *idx_out, *val_out;       // the task's wire-form outputs, typed by flag
+    float *grad, *resid;           // error feedback (resid null: pack only)
+    uint64_t n;
+    uint32_t count;                // min(idx_cap, n) pairs
+    uint32_t flag, blk0;
+    uint32_t zero0;                // idx_cap > count: the unused slots' index 0 is zeroed too
+};
+struct SendFinishBatch {
+    SendFinish t[SEND_BATCH];
+    uint32_t nt;
+};
+static_assert(sizeof(SendFinishBatch) <= 2048, "kernel arguments: stay well under 4 KiB");
+hipError_t launch_ef_pack_batch(const SendFinishBatch &w, uint32_t blocks, hipStream_t s);
 struct WireRx {  // one received stream of a batched decode
     const void *idx_in, *val_in;
     uint32_t *idx;

@@ -128,6 +128,36 @@ class CodecEngine:
                                                         residuals=[residual.reshape(-1)])
         return idx, val, cnt
 
+    def send_buckets(self, items, world: int = 1, fp16_values: bool = False):
+        """The sender side of one iteration in one call
+        (``Compressor.merge_send_batch_async``): for every item ``(key,
+        grads[, residual])`` ModuleCpuGather::run over ``grads`` (this rank's
+        slices, ``grads[0]`` the bucket), ``compress_bucket``'s MERGE compress
+        with the error feedback when ``residual`` is given, and queueTx's
+        packing.  Per tensor the pair count is ``merge_numel(n, ratio, world)``
+        and the wire form ``wire_flag(n, fp16_values)``.  Returns ``(streams,
+        counts)``: per item ``(idx, val, flag)`` with ``numel * world`` zeroed
+        slots in the flag's types, the first ``numel`` this node's stream in the
+        form the ring sends, and the int32 counts tensor (no host sync)."""
+        import torch
+        send, streams = [], []
+        for it in items:
+            key, grads = it[0], list(it[1])
+            residual = it[2] if len(it) > 2 else None
+            if not all(t.is_contiguous() for t in grads + ([residual] if residual is not None else [])):
+                raise ValueError("send_buckets: gradients and residual must be contiguous")
+            n = grads[0].numel()
+            numel = merge_numel(n, self.compression_ratio_, world)
+            flag = wire_flag(n, fp16_values)
+            di, dv = _wire_dtypes(flag)
+            idx = torch.zeros(numel * world, dtype=di, device=grads[0].device)
+            val = torch.zeros(numel * world, dtype=dv, device=grads[0].device)
+            send.append((key, [g.reshape(-1) for g in grads], numel, idx[:numel], val[:numel],
+                         residual.reshape(-1) if residual is not None else None, flag))
+            streams.append((idx, val, flag))
+        counts = self.compressor_.merge_send_batch_async(send)
+        return streams, counts
+
 
 def scatter_merge(idx, val, per_rank: int, world: int, n: int, dense=None, mark=None, out_idx=None, out_val=None,
                   count=None):
