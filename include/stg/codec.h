@@ -221,6 +221,13 @@ int stg_codec_get_timing(stg_codec_t h, double *ms3, uint64_t *calls);
  * for `stream` (phase stamps of builds with STG_FILL_STAMPS); syncs. */
 int stg_codec_debug_words(stg_codec_t h, void *stream, uint32_t *out, int n);
 
+/* Diagnostics: workgroups a batched thresholdv16 scan launch of `chunks`
+ * 128 KiB chunks gets on a device of num_cu CUs when `streams` distinct
+ * streams launched the device's recent scans and the process has hw_queues
+ * hardware queues.  Plain host arithmetic: needs no device.  0 on a bad
+ * argument. */
+int stg_debug_tv16_scan_grid(int num_cu, int streams, int hw_queues, uint32_t chunks);
+
 /* Checks the device-side failure word of every workspace of this handle
  * (e.g. a regime-B candidate set larger than the build supports); syncs. */
 int stg_codec_check(stg_codec_t h);

@@ -27,6 +27,7 @@
 #include <dlfcn.h>
 
 #include "../../include/stg/codec.h"
+#include "scan_grid.h"
 #include "ws.h"
 
 namespace {
@@ -374,13 +375,54 @@ std::string state_key(Method m, const char *key, const void *src) {
 //    records no events at all: concurrent callers on their own streams
 //    overlap freely (the reference's per-task compress() from many pool
 //    workers, engine/modules/compress.cpp:141, core_module_api.cpp:7-24).
+//  * The streams of the device's last 16 batched launches (all handles of
+//    the process) size a launch's grid: see launch_tv16_group.
 struct FusedLane {
     std::mutex mu;
     std::vector<std::pair<hipEvent_t, hipStream_t>> inflight;  // oldest first
     std::vector<hipEvent_t> pool;
+    static constexpr uint32_t RING = 16;
+    hipStream_t ring[RING] = {};
+    uint32_t ring_n = 0, ring_at = 0;
+    // Records a batched launch on stream s; returns the distinct streams among
+    // the last RING launches, this one included (caller holds mu).
+    uint32_t note_stream(hipStream_t s) {
+        ring[ring_at] = s;
+        ring_at = (ring_at + 1) % RING;
+        ring_n = std::min(ring_n + 1, RING);
+        uint32_t distinct = 0;
+        for (uint32_t i = 0; i < ring_n; ++i) {
+            bool seen = false;
+            for (uint32_t j = 0; j < i; ++j) seen |= ring[j] == ring[i];
+            distinct += !seen;
+        }
+        return distinct;
+    }
 };
 
 FusedLane g_lanes[64];
+
+// Hardware queues of the process: GPU_MAX_HW_QUEUES as the HIP runtime reads
+// it (default 4).  Only read, never set.
+uint32_t hw_queues() {
+    static const uint32_t v = [] {
+        const char *e = getenv("GPU_MAX_HW_QUEUES");
+        const int x = e ? atoi(e) : 4;
+        return (uint32_t)std::max(1, x);
+    }();
+    return v;
+}
+
+// Diagnostics: STG_DEBUG_TV16_GRID = workgroups of every thresholdv16 scan
+// launch (1 .. TV16_MAXG; unset or 0: the policy above).  Read once.
+uint32_t forced_grid() {
+    static const uint32_t v = [] {
+        const char *e = getenv("STG_DEBUG_TV16_GRID");
+        const int x = e ? atoi(e) : 0;
+        return x <= 0 ? 0u : std::min<uint32_t>((uint32_t)x, stg::TV16_MAXG);
+    }();
+    return v;
+}
 
 uint32_t fused_inflight() {  // 0: unlimited
     static const uint32_t v = [] {
@@ -451,17 +493,20 @@ int launch_tv16_group(stg_codec *h, Workspace *ws, std::vector<stg::Tv16Bucket> 
     a.num_cu = h->num_cu;
     a.ev = timed ? evs.data() : nullptr;
     a.epoch = ws->epoch;
-    // Workgroups are dealt round-robin over the 8 XCDs (32 CUs, 64 slots
-    // each): a launch's share is a multiple of 8 so every XCD holds the same
-    // number of each launch's workgroups.
     const uint32_t inflight = fused_inflight();
-    constexpr uint32_t XCDS = 8;
-    // Every launch may use the whole chip (two scan workgroups per CU): with
-    // dynamic chunk takes, the workgroups of concurrent launches simply
-    // interleave as slots free up (an even split of the slots between the
-    // in-flight launches measured no faster).
+    // A one-bucket launch may use the whole chip (two scan workgroups per
+    // CU).  A batched launch takes its share of it by the streams that
+    // launched the device's last scans (scan_grid.h): workgroups past what the
+    // launch can keep streaming start only after its chunks are gone, take
+    // nothing and leave, holding slots other launches' workgroups wait for.
     a.max_wg = (uint32_t)(2 * h->num_cu);
-    (void)XCDS;
+    if (grp.size() > 1) {
+        FusedLane &lane = g_lanes[h->device & 63];
+        std::lock_guard<std::mutex> lg(lane.mu);
+        chunks = std::min<size_t>(chunks, 0xffffffffu);
+        a.max_wg = stg::tv16_scan_grid((uint32_t)h->num_cu, lane.note_stream(s), hw_queues(), (uint32_t)chunks);
+    }
+    if (const uint32_t forced = forced_grid()) a.max_wg = forced;
     a.desc_cap = (uint32_t)std::min<size_t>(ws->cap_desc, 0xffffffffu);
     a.lone_cap = (uint32_t)ws->cap_lone;
     a.lone_calls = &ws->lone_calls;
@@ -1176,8 +1221,21 @@ int stg_codec_check(stg_codec_t h) {
             }
             return fail(STG_ERR_DEVICE, m);
         }
+        // diagnostics (STG_DEBUG_TV16_COUNT): the scan's counters of this workspace
+        static const bool count = getenv("STG_DEBUG_TV16_COUNT") && atoi(getenv("STG_DEBUG_TV16_COUNT")) != 0;
+        if (count) {
+            uint32_t w[5] = {};
+            HIP_TRY(hipMemcpy(w, kv.second->d.misc, sizeof w, hipMemcpyDeviceToHost));
+            fprintf(stderr, "stg: tv16 scan counters, stream %p: launches %u, dead workgroups %u (most in one launch %u)\n",
+                    (void *)kv.first, w[4], w[1], w[2]);
+        }
     }
     return STG_OK;
+}
+
+int stg_debug_tv16_scan_grid(int num_cu, int streams, int hw_queues, uint32_t chunks) {
+    if (num_cu < 1 || streams < 0 || hw_queues < 0) return 0;
+    return (int)stg::tv16_scan_grid((uint32_t)num_cu, (uint32_t)streams, (uint32_t)hw_queues, chunks);
 }
 
 int stg_codec_debug_words(stg_codec_t h, void *stream, uint32_t *out, int n) {

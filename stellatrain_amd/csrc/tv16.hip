@@ -42,6 +42,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "scan_grid.h"
 #include "tv16_dev.h"
 
 namespace stg {
@@ -76,7 +77,6 @@ constexpr uint32_t SCAN_D_BATCH = kTv16ScanD;
 // halve its round trips; 6 waves per SIMD leave it ~80 VGPRs.
 constexpr uint32_t kTv16ScanDLone = 6;
 constexpr uint32_t SCAN_D_LONE = kTv16ScanDLone;
-constexpr uint32_t MAXG = 512;      // workgroups per launch (2 per CU)
 // ---------------------------------------------------------------------------
 // first call: sequential |x| sums per line, last partial line scaled by
 // 16/(n%16) (thresholdv16.cpp:44-50)
@@ -135,7 +135,12 @@ struct BatchArgs {
     ChunkDesc *desc;
     uint32_t *cand;
     uint32_t *fail;
+    uint32_t *dbg;   // diagnostics (STG_DEBUG_TV16_COUNT; null: off): ws.misc, DBG_* words below
 };
+// Debug words of the scan: workgroups that left without ever taking a chunk
+// (sum; the most in one launch) and launches.
+constexpr uint32_t DBG_DEAD = 1, DBG_DEAD_MAX = 2, DBG_LAUNCHES = 4;
+constexpr uint32_t CC_DEAD = 16;  // CallCtl::pad word of the launch's own dead count (debug only)
 
 // LDS of one workgroup (< 80 KiB: two workgroups per CU).
 struct Lds {
@@ -197,7 +202,7 @@ struct Ctx {
         }
         for (uint32_t b = 0; b < A.nbk; ++b) st_sc1(A.bk[b].count_out, POISON_COUNT);
     }
-    // bucket holding global chunk k (scalar search over <= 16 buckets)
+    // bucket holding global chunk k (scalar search over <= MAX_BATCH buckets)
     __device__ __forceinline__ uint32_t bucket_of(uint32_t k) const {
         uint32_t b = 0;
         while (b + 1 < A.nbk && k >= A.bk[b + 1].cs) ++b;
@@ -651,7 +656,16 @@ tv16_batch(BatchArgs A) {
         // workgroup's slots therefore hold increasing chunks, chunks are taken
         // in order, and a chunk is only ever taken by a running workgroup: no
         // wait in this launch points at a workgroup that is not resident.
-        L.cid[0] = g_add(&C.cc()->next, 1u);
+        const uint32_t k0 = g_add(&C.cc()->next, 1u);
+        L.cid[0] = k0;
+        if (A.dbg) {  // diagnostics: launches, and workgroups that never take a chunk
+            if (C.w == 0) g_add(A.dbg + DBG_LAUNCHES, 1u);
+            if (k0 >= A.K) {
+                g_add(A.dbg + DBG_DEAD, 1u);
+                const uint32_t mine = g_add(&C.cc()->pad[CC_DEAD], 1u) + 1u;
+                __hip_atomic_fetch_max(gp(A.dbg + DBG_DEAD_MAX), mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
         for (uint32_t i = 0; i < CIDR; ++i) { L.cok[i] = 0; L.mid[i] = 0; }
         L.cok[0] = 1;
     }
@@ -783,10 +797,14 @@ hipError_t launch_tv16(const Tv16Launch &a, const DevWS &ws, hipStream_t s) {
     A.desc = ws.desc;
     A.cand = ws.cand;
     A.fail = ws.fail;
-    // this launch's share of the device's two scan workgroups per CU
-    // (all of them for one stream; launches from several streams split them);
-    // no more than there are chunks.  Co-residency is not required.
-    const uint32_t G = std::max<uint32_t>(1, std::min<uint32_t>(std::min<uint32_t>(a.max_wg, K), MAXG));
+    // this launch's share of the device's two scan workgroups per CU, sized
+    // by the caller (scan_grid.h: all of them for one stream, launches from
+    // several streams split them with some oversubscription; no more than the
+    // chunks need).  Chunks are taken dynamically: any G >= 1 gives the same
+    // result, and co-residency is not required.
+    const uint32_t G = std::max<uint32_t>(1, std::min<uint32_t>(a.max_wg, TV16_MAXG));
+    static const bool dbg_count = getenv("STG_DEBUG_TV16_COUNT") && atoi(getenv("STG_DEBUG_TV16_COUNT")) != 0;
+    A.dbg = dbg_count ? ws.misc : nullptr;
     const bool lone_scan = lone_ok && a.nb == 1;
     const uint32_t KL = lone_chunks(a.b[0].n);  // one-bucket chunks
     if (lone_path) {
