@@ -27,6 +27,8 @@
 #include <dlfcn.h>
 
 #include "../../include/stg/codec.h"
+#include "batch_pack.h"
+#include "devbuf.h"
 #include "scan_grid.h"
 #include "ws.h"
 
@@ -39,6 +41,9 @@ int fail(int code, const std::string &msg) {
     return code;
 }
 
+// a switch's value as read with getenv (unset: dflt)
+int env_int(const char *e, int dflt) { return e ? atoi(e) : dflt; }
+
 #define HIP_TRY(expr)                                                                        \
     do {                                                                                     \
         hipError_t e_ = (expr);                                                              \
@@ -49,56 +54,65 @@ enum Method { M_TV16 = 0, M_TV = 1, M_TOPK = 2, M_TOPK_EXACT = 3 };
 
 constexpr uint32_t SLOTS_PER_CHUNK = 4096;
 
+// "current device and its CU count" for the entries that take no handle
+// (the count of a device never changes: cached per device)
+int device_cus(int *ncu, int *dev = nullptr) {
+    static std::mutex mu;
+    static std::unordered_map<int, int> cus;
+    int d = 0;
+    HIP_TRY(hipGetDevice(&d));
+    if (dev) *dev = d;
+    std::lock_guard<std::mutex> g(mu);
+    auto it = cus.find(d);
+    if (it == cus.end()) {
+        int n = 256;
+        HIP_TRY(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d));
+        it = cus.emplace(d, n).first;
+    }
+    *ncu = it->second;
+    return STG_OK;
+}
+
+// the one-bucket path's lists (tv16lone.hip) as one chunk's worth each, so the
+// four buffers count their capacities in chunks
+struct LqChunk { uint32_t w[stg::LQCAP]; };
+struct LwChunk { uint2 w[stg::LWCAP]; };
+struct LvChunk { float4 v[stg::LQCAP * 4]; };
+
 struct Workspace {
     int device = 0;
     hipStream_t stream = nullptr;
     std::mutex mu;
-    stg::DevWS d{};
-    void *fixed = nullptr;
-    size_t cap_sums = 0, cap_tiles = 0, cap_stage = 0, cap_desc = 0, cap_lone = 0;
+    stg::DevWS d{};  // what the launchers take: set by init() and publish()
+    // Grow-only scratch, each buffer with its own capacity.  Growing waits for
+    // this stream's in-flight work.
+    stg::DevBuf<char> fixed;
+    stg::DevBuf<float> sums, stage_val;
+    stg::DevBuf<uint32_t> tile_cnt, tile_aux, stage_pos;
+    stg::DevBuf<stg::ChunkDesc> desc;
+    stg::DevBuf<uint2> ldesc;
+    stg::DevBuf<LqChunk> lq;
+    stg::DevBuf<LwChunk> lw;
+    stg::DevBuf<LvChunk> lv;
     uint32_t epoch = 0;  // thresholdv16 call counter (hand-off tags)
     uint32_t tk_tag = 0; // one-launch top-k call counter (topk1.hip)
     uint32_t lone_calls = 0;  // thresholdv16 one-bucket path calls (tv16.hip: parity of its per-call blocks)
-    // threshold-v: the ticket's value at the next call, the last call's
-    // range-descriptor tag and the descriptor block last zeroed (tile_cnt, its size)
+    // threshold-v: the ticket's value at the next call and the last call's
+    // range-descriptor tag
     uint64_t tv_base = 0;
     uint32_t tv_tag = 0;
-    uint32_t *tv_desc = nullptr;
-    size_t tv_desc_cap = 0;
     // device buffers of the host-memory entry point
-    float *h_src = nullptr;
-    size_t cap_src = 0;
-    uint32_t *h_idx = nullptr;
-    float *h_val = nullptr;
-    size_t cap_out = 0;
-    uint32_t *h_count = nullptr;
+    stg::DevBuf<float> h_src, h_val;
+    stg::DevBuf<uint32_t> h_idx, h_count;
     uint32_t *pinned_count = nullptr;
     // one-bucket wire path staging (stg_codec_compress_wire_batch_device)
     std::mutex wire_mu;
-    uint32_t *wst_pos = nullptr;
-    float *wst_val = nullptr;
-    size_t cap_wst = 0;
+    stg::DevBuf<uint32_t> wst_pos;
+    stg::DevBuf<float> wst_val;
 
     ~Workspace() {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
-        (void)hipFree(fixed);
-        (void)hipFree(d.sums);
-        (void)hipFree(d.desc);
-        (void)hipFree(d.tile_cnt);
-        (void)hipFree(d.tile_aux);
-        (void)hipFree(d.stage_pos);
-        (void)hipFree(d.stage_val);
-        (void)hipFree(d.ldesc);
-        (void)hipFree(d.lq);
-        (void)hipFree(d.lw);
-        (void)hipFree(d.lv);
-        (void)hipFree(h_src);
-        (void)hipFree(h_idx);
-        (void)hipFree(h_val);
-        (void)hipFree(h_count);
-        (void)hipFree(wst_pos);
-        (void)hipFree(wst_val);
         if (pinned_count) (void)hipHostFree(pinned_count);
     }
 
@@ -122,12 +136,11 @@ struct Workspace {
         const size_t o_crew = carve(sizeof(stg::CrewCtl) * stg::MAX_BATCH);
         const size_t o_tkc = carve(sizeof(stg::TopkCtl) * 2);
         const size_t o_tkf = carve(sizeof(uint32_t) * 2 * stg::TK2_FINE);
-        HIP_TRY(hipMalloc(&fixed, off));
         // zeroed on this workspace's stream: the launches that read the
         // control block are ordered after it (a plain hipMemset runs on the
         // null stream, which a non-blocking stream does not wait for)
-        HIP_TRY(hipMemsetAsync(fixed, 0, off, stream));
-        char *b = static_cast<char *>(fixed);
+        HIP_TRY(fixed.reserve(off, stream, true));
+        char *b = fixed.get();
         d.ctl = reinterpret_cast<stg::FillCtl *>(b + o_ctl);
         d.cp = reinterpret_cast<stg::CallParams *>(b + o_cp);
         d.rsel = reinterpret_cast<stg::RSel *>(b + o_rs);
@@ -144,28 +157,26 @@ struct Workspace {
         return STG_OK;
     }
 
-    // Grow-only scratch.  Growing waits for this stream's in-flight work.
-    template <typename T>
-    int grow(T *&p, size_t &cap, size_t need) {
-        if (need <= cap) return STG_OK;
-        HIP_TRY(hipStreamSynchronize(stream));
-        (void)hipFree(p);
-        p = nullptr;
-        const size_t n = std::max<size_t>(need, cap + cap / 2);
-        HIP_TRY(hipMalloc(&p, n * sizeof(T)));
-        cap = n;
+    // The grown buffers as the launchers see them; every sizing routine ends
+    // here, whatever it returns, so d never names a freed block.
+    int publish(hipError_t e) {
+        d.sums = sums.get();
+        d.desc = desc.get();
+        d.tile_cnt = tile_cnt.get();
+        d.tile_aux = tile_aux.get();
+        d.stage_pos = stage_pos.get();
+        d.stage_val = stage_val.get();
+        d.ldesc = ldesc.get();
+        d.lq = reinterpret_cast<uint32_t *>(lq.get());
+        d.lw = reinterpret_cast<uint2 *>(lw.get());
+        d.lv = reinterpret_cast<float4 *>(lv.get());
+        if (e != hipSuccess) return fail(STG_ERR_HIP, std::string("workspace scratch: ") + hipGetErrorString(e));
         return STG_OK;
     }
 
     // thresholdv16 chunk descriptors: zeroed on (re)allocation, so no stale
     // word carries a live call tag (epochs start at 1)
-    int ensure_desc(size_t n) {
-        if (n <= cap_desc) return STG_OK;
-        int rc;
-        if ((rc = grow(d.desc, cap_desc, n))) return rc;
-        HIP_TRY(hipMemsetAsync(d.desc, 0, cap_desc * sizeof(stg::ChunkDesc), stream));
-        return STG_OK;
-    }
+    int ensure_desc(size_t n) { return publish(desc.reserve(n, stream, true)); }
 
     // one-bucket path lists (tv16lone.hip): per chunk a tagged count pair and
     // the qualifying / window line lists.  The finish inside the scan launch
@@ -176,61 +187,39 @@ struct Workspace {
     // otherwise already hold a live tag with another call's counts.  Tags are
     // >= 1 and only this workspace writes its pairs afterwards, so no stale
     // pair ever matches a later call.  The lists themselves are read only
-    // behind a matched pair.
+    // behind a matched pair.  (nc <= LMAXC, which also bounds the growth.)
     int ensure_lone(size_t nc) {
-        if (nc <= cap_lone) return STG_OK;
-        HIP_TRY(hipStreamSynchronize(stream));
-        (void)hipFree(d.ldesc);
-        (void)hipFree(d.lq);
-        (void)hipFree(d.lw);
-        (void)hipFree(d.lv);
-        d.ldesc = nullptr;
-        d.lq = nullptr;
-        d.lw = nullptr;
-        d.lv = nullptr;
-        const size_t c = std::min<size_t>(stg::LMAXC, std::max(nc, cap_lone + cap_lone / 2));
-        cap_lone = 0;
-        HIP_TRY(hipMalloc(&d.ldesc, c * sizeof(uint2)));
-        HIP_TRY(hipMalloc(&d.lq, c * stg::LQCAP * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&d.lw, c * stg::LWCAP * sizeof(uint2)));
-        HIP_TRY(hipMalloc(&d.lv, c * stg::LQCAP * 4 * sizeof(float4)));
-        static const bool stale = getenv("STG_DEBUG_LDESC_STALE") && atoi(getenv("STG_DEBUG_LDESC_STALE")) == 1;
-        if (stale) {  // diagnostics: what a recycled block looks like (every pair tagged 1..8, counts 0)
-            std::vector<uint2> p(c);
-            for (size_t i = 0; i < c; ++i) p[i] = make_uint2(0u, 1u + (uint32_t)(i & 7u));
-            HIP_TRY(hipMemcpyAsync(d.ldesc, p.data(), c * sizeof(uint2), hipMemcpyHostToDevice, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-        } else {
-            HIP_TRY(hipMemsetAsync(d.ldesc, 0, c * sizeof(uint2), stream));
+        static const bool stale = env_int(getenv("STG_DEBUG_LDESC_STALE"), 0) == 1;
+        bool fresh = false;
+        hipError_t e = ldesc.reserve(nc, stream, !stale, &fresh, stg::LMAXC);
+        if (e == hipSuccess) e = lq.reserve(nc, stream, false, nullptr, stg::LMAXC);
+        if (e == hipSuccess) e = lw.reserve(nc, stream, false, nullptr, stg::LMAXC);
+        if (e == hipSuccess) e = lv.reserve(nc, stream, false, nullptr, stg::LMAXC);
+        if (e == hipSuccess && fresh && stale) {  // diagnostics: what a recycled block looks like (every pair tagged 1..8, counts 0)
+            std::vector<uint2> p(ldesc.cap());
+            for (size_t i = 0; i < p.size(); ++i) p[i] = make_uint2(0u, 1u + (uint32_t)(i & 7u));
+            e = hipMemcpyAsync(ldesc.get(), p.data(), p.size() * sizeof(uint2), hipMemcpyHostToDevice, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
         }
-        cap_lone = c;
-        return STG_OK;
+        return publish(e);
     }
+    // chunks every one-bucket list holds
+    size_t lone_cap() const { return std::min({ldesc.cap(), lq.cap(), lw.cap(), lv.cap()}); }
 
     int ensure_wire_stage(size_t n) {  // (caller holds wire_mu)
-        size_t c = cap_wst;
-        int rc;
-        if ((rc = grow(wst_pos, c, n))) return rc;
-        c = cap_wst;
-        if ((rc = grow(wst_val, c, n))) return rc;
-        cap_wst = c;
+        HIP_TRY(wst_pos.reserve(n, stream, false));
+        HIP_TRY(wst_val.reserve(n, stream, false));
         return STG_OK;
     }
 
-    int ensure(size_t sums, size_t tiles, size_t stage) {
-        int rc;
-        if ((rc = grow(d.sums, cap_sums, sums))) return rc;
-        size_t ct = cap_tiles;
-        if ((rc = grow(d.tile_cnt, ct, tiles))) return rc;
-        ct = cap_tiles;
-        if ((rc = grow(d.tile_aux, ct, tiles))) return rc;
-        cap_tiles = ct;
-        size_t cs = cap_stage;
-        if ((rc = grow(d.stage_pos, cs, stage))) return rc;
-        cs = cap_stage;
-        if ((rc = grow(d.stage_val, cs, stage))) return rc;
-        cap_stage = cs;
-        return STG_OK;
+    // zero_tiles: the tile words carry call tags (threshold-v), so fresh memory is zeroed
+    int ensure(size_t nsums, size_t tiles, size_t stage, bool zero_tiles = false) {
+        hipError_t e = sums.reserve(nsums, stream, false);
+        if (e == hipSuccess) e = tile_cnt.reserve(tiles, stream, zero_tiles);
+        if (e == hipSuccess) e = tile_aux.reserve(tiles, stream, zero_tiles);
+        if (e == hipSuccess) e = stage_pos.reserve(stage, stream, false);
+        if (e == hipSuccess) e = stage_val.reserve(stage, stream, false);
+        return publish(e);
     }
 };
 
@@ -243,7 +232,7 @@ struct stg_codec {
     std::string name;
     std::mutex mu;
     std::unordered_map<std::string, uint32_t> slot_of;
-    std::vector<KeyState *> chunks;
+    std::vector<stg::DevBuf<KeyState>> chunks;  // never-moving blocks of SLOTS_PER_CHUNK states
     uint32_t nslots = 0;
     std::unordered_map<hipStream_t, std::unique_ptr<Workspace>> ws;
     // kernel timing (stg_codec_set_timing)
@@ -255,7 +244,6 @@ struct stg_codec {
     ~stg_codec() {
         (void)hipSetDevice(device);
         ws.clear();
-        for (auto *c : chunks) (void)hipFree(c);
         for (auto *v : {&ev_pending, &ev_pool})
             for (auto &e : *v)
                 for (auto x : e) (void)hipEventDestroy(x);
@@ -272,7 +260,7 @@ struct stg_codec {
         return STG_OK;
     }
 
-    KeyState *slot_ptr(uint32_t s) { return chunks[s / SLOTS_PER_CHUNK] + (s % SLOTS_PER_CHUNK); }
+    KeyState *slot_ptr(uint32_t s) { return chunks[s / SLOTS_PER_CHUNK].get() + (s % SLOTS_PER_CHUNK); }
 
     // Returns the state slot of `key`; *fresh = true when it was just created.
     int slot(const std::string &key, KeyState **out, bool *fresh) {
@@ -280,12 +268,11 @@ struct stg_codec {
         auto it = slot_of.find(key);
         if (it != slot_of.end()) { *out = slot_ptr(it->second); *fresh = false; return STG_OK; }
         if (nslots % SLOTS_PER_CHUNK == 0) {
-            KeyState *c = nullptr;
-            HIP_TRY(hipMalloc(&c, sizeof(KeyState) * SLOTS_PER_CHUNK));
+            stg::DevBuf<KeyState> c;
             // states are read on any stream: zero them before any launch sees them
-            HIP_TRY(hipMemsetAsync(c, 0, sizeof(KeyState) * SLOTS_PER_CHUNK, nullptr));
+            HIP_TRY(c.reserve(SLOTS_PER_CHUNK, nullptr, true));
             HIP_TRY(hipStreamSynchronize(nullptr));
-            chunks.push_back(c);
+            chunks.push_back(std::move(c));
         }
         const uint32_t s = nslots++;
         slot_of.emplace(key, s);
@@ -315,42 +302,37 @@ struct stg_sgd {
     bool nesterov, maximize;
     uint32_t iter = 0;
     std::mutex mu;
-    std::unordered_map<std::string, std::pair<float *, uint32_t>> mom;
+    // per-name state: the buffer and the param_len it was created for
+    template <typename T>
+    struct Named {
+        stg::DevBuf<T> buf;
+        uint32_t len = 0;
+    };
+    std::unordered_map<std::string, Named<float>> mom;
     // smart momentum (sgd.cpp:54, 225-232, 258-259)
     bool smart = false;
-    std::unordered_map<std::string, std::pair<uint32_t *, uint32_t>> last;  // per name, zeroed when first needed
-    float *pow_tab = nullptr;  // pow(momentum, d), d < pow_len; built once (the momentum never changes), kept until destroy
-    uint32_t pow_len = 0;
-    uint32_t *fail = nullptr;  // device failure word (SGD_FAIL_FACTOR)
-    ~stg_sgd() {
-        (void)hipSetDevice(device);
-        for (auto &kv : mom) (void)hipFree(kv.second.first);
-        for (auto &kv : last) (void)hipFree(kv.second.first);
-        (void)hipFree(pow_tab);
-        (void)hipFree(fail);
-    }
+    std::unordered_map<std::string, Named<uint32_t>> last;  // per name, zeroed when first needed
+    stg::DevBuf<float> pow_tab;  // pow(momentum, d), d < its capacity; built once (the momentum never changes), kept until destroy
+    stg::DevBuf<uint32_t> fail;  // device failure word (SGD_FAIL_FACTOR)
+    ~stg_sgd() { (void)hipSetDevice(device); }  // (the members free on this device)
 };
 
 struct stg_adam {
     int device = 0;
-    uint32_t *fail = nullptr;  // device failure word (amsgrad look-back timeout)
+    stg::DevBuf<uint32_t> fail;  // device failure word (amsgrad look-back timeout)
     float lr, b1, b2, eps, weight_decay;
     bool amsgrad, maximize;
     struct Name {
-        float *m = nullptr, *v = nullptr, *vmax = nullptr;
-        uint32_t *tiles = nullptr;  // amsgrad look-back words, one uint64 per ADAM_TILE of param_len
+        stg::DevBuf<float> mvv;       // one allocation: m | v | vmax (L, L and 1 floats, L = max(len, 1))
+        stg::DevBuf<uint64_t> tiles;  // amsgrad look-back words, one per ADAM_TILE of param_len
         uint32_t len = 0, tick = 1;
+        float *m() const { return mvv.get(); }
+        float *v() const { return mvv.get() + std::max<size_t>(len, 1); }
+        float *vmax() const { return mvv.get() + 2 * std::max<size_t>(len, 1); }
     };
     std::mutex mu;
     std::unordered_map<std::string, Name> st;
-    ~stg_adam() {
-        (void)hipSetDevice(device);
-        (void)hipFree(fail);
-        for (auto &kv : st) {
-            (void)hipFree(kv.second.m);
-            (void)hipFree(kv.second.tiles);
-        }
-    }
+    ~stg_adam() { (void)hipSetDevice(device); }  // (the members free on this device)
 };
 
 namespace {
@@ -405,33 +387,20 @@ FusedLane g_lanes[64];
 // Hardware queues of the process: GPU_MAX_HW_QUEUES as the HIP runtime reads
 // it (default 4).  Only read, never set.
 uint32_t hw_queues() {
-    static const uint32_t v = [] {
-        const char *e = getenv("GPU_MAX_HW_QUEUES");
-        const int x = e ? atoi(e) : 4;
-        return (uint32_t)std::max(1, x);
-    }();
+    static const uint32_t v = (uint32_t)std::max(1, env_int(getenv("GPU_MAX_HW_QUEUES"), 4));
     return v;
 }
 
 // Diagnostics: STG_DEBUG_TV16_GRID = workgroups of every thresholdv16 scan
 // launch (1 .. TV16_MAXG; unset or 0: the policy above).  Read once.
 uint32_t forced_grid() {
-    static const uint32_t v = [] {
-        const char *e = getenv("STG_DEBUG_TV16_GRID");
-        const int x = e ? atoi(e) : 0;
-        return x <= 0 ? 0u : std::min<uint32_t>((uint32_t)x, stg::TV16_MAXG);
-    }();
+    static const uint32_t v =
+        (uint32_t)std::min<int>(std::max(0, env_int(getenv("STG_DEBUG_TV16_GRID"), 0)), stg::TV16_MAXG);
     return v;
 }
 
 uint32_t fused_inflight() {  // 0: unlimited
-    static const uint32_t v = [] {
-        if (const char *e = getenv("STG_TV16_INFLIGHT")) {
-            const int x = atoi(e);
-            return x <= 0 ? 0u : (uint32_t)std::min(4, x);
-        }
-        return 0u;
-    }();
+    static const uint32_t v = (uint32_t)std::min(4, std::max(0, env_int(getenv("STG_TV16_INFLIGHT"), 0)));
     return v;
 }
 
@@ -468,7 +437,7 @@ int launch_tv16_group(stg_codec *h, Workspace *ws, std::vector<stg::Tv16Bucket> 
     if ((rc = ws->ensure(need, 1, 1))) return rc;
     size_t off = 0, chunks = 0;
     for (auto &b : grp) {
-        b.sums = ws->d.sums + off;
+        b.sums = ws->sums.get() + off;
         off += 2 * ((b.n + 15) / 16 + 64);
         chunks += std::max<size_t>(1, (b.n / 16 + stg::TV16_CHUNK - 1) / stg::TV16_CHUNK);
     }
@@ -485,7 +454,7 @@ int launch_tv16_group(stg_codec *h, Workspace *ws, std::vector<stg::Tv16Bucket> 
     if (++ws->epoch >= (1u << 24)) {
         ws->epoch = 1;
         HIP_TRY(hipMemsetAsync(ws->d.ctl, 0, sizeof(stg::FillCtl), s));
-        HIP_TRY(hipMemsetAsync(ws->d.desc, 0, ws->cap_desc * sizeof(stg::ChunkDesc), s));
+        HIP_TRY(hipMemsetAsync(ws->desc.get(), 0, ws->desc.cap() * sizeof(stg::ChunkDesc), s));
     }
     stg::Tv16Launch a{};
     a.b = grp.data();
@@ -507,8 +476,8 @@ int launch_tv16_group(stg_codec *h, Workspace *ws, std::vector<stg::Tv16Bucket> 
         a.max_wg = stg::tv16_scan_grid((uint32_t)h->num_cu, lane.note_stream(s), hw_queues(), (uint32_t)chunks);
     }
     if (const uint32_t forced = forced_grid()) a.max_wg = forced;
-    a.desc_cap = (uint32_t)std::min<size_t>(ws->cap_desc, 0xffffffffu);
-    a.lone_cap = (uint32_t)ws->cap_lone;
+    a.desc_cap = (uint32_t)std::min<size_t>(ws->desc.cap(), 0xffffffffu);
+    a.lone_cap = (uint32_t)ws->lone_cap();
     a.lone_calls = &ws->lone_calls;
     if (!inflight) {  // no admission: nothing to track
         HIP_TRY(stg::launch_tv16(a, ws->d, s));
@@ -622,13 +591,8 @@ int run_device(stg_codec *h, const char *key, const float *d_src, const void *ke
         bool fresh;
         if ((rc = h->slot(state_key(h->method, key, key_ptr), &st, &fresh))) return rc;
         // range descriptors (tv.hip): counts at tile_cnt, maxima at tile_aux, two words per range
-        if ((rc = ws->ensure(1, 2 * (size_t)stg::TV_MAXG, 1))) return rc;
-        if (ws->tv_desc != ws->d.tile_cnt || ws->tv_desc_cap != ws->cap_tiles) {  // fresh memory: no stale tags
-            HIP_TRY(hipMemsetAsync(ws->d.tile_cnt, 0, ws->cap_tiles * sizeof(uint32_t), s));
-            HIP_TRY(hipMemsetAsync(ws->d.tile_aux, 0, ws->cap_tiles * sizeof(uint32_t), s));
-            ws->tv_desc = ws->d.tile_cnt;
-            ws->tv_desc_cap = ws->cap_tiles;
-        }
+        // (zeroed when fresh: no stale tags)
+        if ((rc = ws->ensure(1, 2 * (size_t)stg::TV_MAXG, 1, true))) return rc;
         if (++ws->tv_tag == 0) ws->tv_tag = 1;
         uint32_t grid = 0;
         stg::TvLaunch a{d_src, n, k, (uint32_t)idx_cap, d_idx, d_val, d_count, st, fresh, h->num_cu, ev,
@@ -666,25 +630,16 @@ int run_device(stg_codec *h, const char *key, const float *d_src, const void *ke
 struct MergeScratch {
     std::mutex mu;
     int device = 0;
-    uint32_t *tiles = nullptr, *win = nullptr;
-    size_t cap_tiles = 0, cap_win = 0;
-    // world == 1 in one launch: tagged per-tile counts (cap_tiles of them, zeroed
+    stg::DevBuf<uint32_t> tiles, win;
+    // world == 1 in one launch: tagged per-tile counts (as many as `tiles`, zeroed
     // whenever reallocated); the tile ticket and the duplicate flag
-    uint64_t *desc = nullptr, *ticket = nullptr;
+    stg::DevBuf<uint64_t> desc, ticket;
     uint32_t tag = 0;
-    uint32_t *fail = nullptr;  // sticky device failure word (a look-back that gave up)
+    stg::DevBuf<uint32_t> fail;  // sticky device failure word (a look-back that gave up)
     // batched launches (merge_batch.hip): a ticket, duplicate flag and failed-launch
     // tag per tensor slot, zero at creation; they share win, desc, tag and fail
-    stg::MergeSlotCtl *bctl = nullptr;
-    ~MergeScratch() {
-        (void)hipSetDevice(device);
-        (void)hipFree(tiles);
-        (void)hipFree(win);
-        (void)hipFree(desc);
-        (void)hipFree(ticket);
-        (void)hipFree(fail);
-        (void)hipFree(bctl);
-    }
+    stg::DevBuf<stg::MergeSlotCtl> bctl;
+    ~MergeScratch() { (void)hipSetDevice(device); }  // (the members free on this device)
 };
 std::mutex g_merge_mu;
 // shared: a caller holds its reference for the whole call, so a concurrent
@@ -705,41 +660,39 @@ int merge_scratch_ensure(MergeScratch *m, hipStream_t s, size_t n, size_t per_ra
     // ... and the world-1 emission's tagged tile counts (tiles of >= MERGE_TILE / 16 pairs)
     const size_t tiles = std::max({2 * ((std::max(n, per_rank) + stg::MERGE_TILE - 1) / stg::MERGE_TILE) + 2,
                                    (per_rank + stg::MERGE_TILE / 16 - 1) / (stg::MERGE_TILE / 16) + 2, min_tiles});
-    if (tiles > m->cap_tiles) {
-        HIP_TRY(hipStreamSynchronize(s));
-        (void)hipFree(m->tiles);
-        m->tiles = nullptr;
-        HIP_TRY(hipMalloc(&m->tiles, tiles * sizeof(uint32_t)));
-        (void)hipFree(m->desc);
-        m->desc = nullptr;
-        HIP_TRY(hipMalloc(&m->desc, tiles * sizeof(uint64_t)));
-        HIP_TRY(hipMemsetAsync(m->desc, 0, tiles * sizeof(uint64_t), s));  // no stale tags
-        m->cap_tiles = tiles;
-    }
-    if (!m->ticket) {  // [0]: the emission's tile ticket; [1]: the duplicate flag (low word)
-        HIP_TRY(hipMalloc(&m->ticket, 2 * sizeof(uint64_t)));
-        HIP_TRY(hipMemsetAsync(m->ticket, 0, 2 * sizeof(uint64_t), s));
-    }
-    if (!m->fail) {  // [0] sticky failure bits, [1] the tag of the last call that failed
-        HIP_TRY(hipMalloc(&m->fail, 2 * sizeof(uint32_t)));
-        HIP_TRY(hipMemsetAsync(m->fail, 0, 2 * sizeof(uint32_t), s));
-    }
-    if (min_tiles && !m->bctl) {
-        HIP_TRY(hipMalloc(&m->bctl, stg::MERGE_BATCH * sizeof(stg::MergeSlotCtl)));
-        HIP_TRY(hipMemsetAsync(m->bctl, 0, stg::MERGE_BATCH * sizeof(stg::MergeSlotCtl), s));
-    }
+    // (sized to the need exactly, as the tile counts always were)
+    HIP_TRY(m->tiles.reserve(tiles, s, false, nullptr, tiles));
+    HIP_TRY(m->desc.reserve(tiles, s, true, nullptr, tiles));  // zeroed: no stale tags
+    // [0]: the emission's tile ticket; [1]: the duplicate flag (low word)
+    HIP_TRY(m->ticket.reserve(2, s, true));
+    // [0] sticky failure bits, [1] the tag of the last call that failed
+    HIP_TRY(m->fail.reserve(2, s, true));
+    if (min_tiles) HIP_TRY(m->bctl.reserve(stg::MERGE_BATCH, s, true));
     const size_t words = std::max<size_t>(world > 1 ? 2 * n : n, 1);  // world > 1: two election halves
-    if (words > m->cap_win) {
-        HIP_TRY(hipStreamSynchronize(s));
-        (void)hipFree(m->win);
-        m->win = nullptr;
-        const size_t c = std::max(words, m->cap_win + m->cap_win / 2);
-        HIP_TRY(hipMalloc(&m->win, c * sizeof(uint32_t)));
-        HIP_TRY(hipMemsetAsync(m->win, 0, c * sizeof(uint32_t), s));
-        m->cap_win = c;
-    }
+    HIP_TRY(m->win.reserve(words, s, true));
     return STG_OK;
 }
+
+// grad[0] += residual + grad[1 .. N-1] as the gather launchers take it
+stg::GatherArgs gather_args(float *dst, const float *resid, const float *const *d_grads, int num_gpus) {
+    stg::GatherArgs g{};
+    g.dst = dst;
+    g.resid = resid;
+    g.nsrc = (uint32_t)num_gpus;
+    for (int i = 1; i < num_gpus; ++i) g.src[i] = d_grads[i];
+    return g;
+}
+
+// The table of one of ws.h's batched launchers on stream s (batch_pack.h): a
+// launch closes at the table's capacity or before its grid would pass `limit`.
+template <class Table>
+auto stream_packer(uint64_t limit, hipError_t (*launch)(const Table &, uint32_t, hipStream_t), hipStream_t s) {
+    return stg::make_packer<Table>(limit, [launch, s](Table &w, uint32_t blocks) -> int {
+        HIP_TRY(launch(w, blocks, s));
+        return STG_OK;
+    });
+}
+constexpr uint64_t GRID_MAX = 0x7fffffffull;  // workgroups of one launch
 
 }  // namespace
 
@@ -799,7 +752,7 @@ struct CritPath {
     static const Api &get() {
         static const Api a = [] {
             Api r;
-            if (!(getenv("STG_ROCTX") && atoi(getenv("STG_ROCTX")) == 1)) return r;
+            if (env_int(getenv("STG_ROCTX"), 0) != 1) return r;
             void *h = dlopen("librocprofiler-sdk-roctx.so", RTLD_NOW | RTLD_GLOBAL);
             if (!h) h = dlopen("/opt/rocm/lib/librocprofiler-sdk-roctx.so", RTLD_NOW | RTLD_GLOBAL);
             if (!h) return r;
@@ -902,8 +855,8 @@ int stg_codec_compress_wire_batch_device(stg_codec_t h, const stg_bucket_t *buck
         // this stream cannot grow (free) it between the compress and the packing
         std::lock_guard<std::mutex> g(ws->wire_mu);
         if ((rc = ws->ensure_wire_stage(std::max<size_t>(b.idx_cap, 1)))) return rc;
-        t.d_idx = ws->wst_pos;
-        t.d_val = ws->wst_val;
+        t.d_idx = ws->wst_pos.get();
+        t.d_val = ws->wst_val.get();
         t.val_cap = t.idx_cap;
         if ((rc = run_tv16(h, &t, 1, s))) return rc;
         const size_t numel = std::min<size_t>(b.idx_cap, b.n);  // the pairs the fill writes
@@ -925,11 +878,7 @@ int stg_merge_gather_compress_device(stg_codec_t h, const stg_bucket_t *bucket, 
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     HIP_TRY(hipSetDevice(h->device));
-    stg::GatherArgs g{};
-    g.dst = const_cast<float *>(b.d_src);
-    g.resid = d_residual;
-    g.nsrc = (uint32_t)num_gpus;
-    for (int i = 1; i < num_gpus; ++i) g.src[i] = d_grads[i];
+    const stg::GatherArgs g = gather_args(const_cast<float *>(b.d_src), d_residual, d_grads, num_gpus);
     if (h->method == M_TV16 && b.n) {
         float *res[1] = {d_residual};
         if ((rc = run_tv16(h, &b, 1, s, d_residual ? res : nullptr, &g))) return rc;
@@ -1005,19 +954,14 @@ int stg_merge_send_batch_device(stg_codec_t h, const stg_send_task_t *tasks, siz
         bk[i] = tasks[i].bucket;
         res[i] = tasks[i].d_residual;
         if (!bk[i].n) continue;  // (run_tv16 writes its zero count)
-        bk[i].d_idx = ws->wst_pos + off;
-        bk[i].d_val = ws->wst_val + off;
+        bk[i].d_idx = ws->wst_pos.get() + off;
+        bk[i].d_val = ws->wst_val.get() + off;
         bk[i].val_cap = bk[i].idx_cap;
         off += slice(bk[i].idx_cap);
     }
     auto gather_of = [&](size_t i) {
         const stg_send_task_t &t = tasks[i];
-        stg::GatherArgs g{};
-        g.dst = const_cast<float *>(t.bucket.d_src);
-        g.resid = t.d_residual;
-        g.nsrc = (uint32_t)t.num_gpus;
-        for (int r = 1; r < t.num_gpus; ++r) g.src[r] = t.d_grads[r];
-        return g;
+        return gather_args(const_cast<float *>(t.bucket.d_src), t.d_residual, t.d_grads, t.num_gpus);
     };
     // One task of 16-64 MiB alone: the one-bucket scan sums the sources in its
     // own streaming pass (tv16lone.hip), one pass over the bucket instead of two.
@@ -1028,15 +972,7 @@ int stg_merge_send_batch_device(stg_codec_t h, const stg_send_task_t *tasks, siz
     } else {
         // gather groups: a launch closes at SEND_BATCH tasks or before its grid
         // would pass num_cu * 8 workgroups (a larger tensor runs alone)
-        stg::SendGatherBatch gb{};
-        uint64_t blocks = 0;
-        const uint64_t cap = (uint64_t)h->num_cu * 8;
-        auto flush = [&]() -> int {
-            if (gb.nt) HIP_TRY(stg::launch_gather_add_batch(gb, (uint32_t)blocks, s));
-            gb = stg::SendGatherBatch{};
-            blocks = 0;
-            return STG_OK;
-        };
+        auto gb = stream_packer<stg::SendGatherBatch>((uint64_t)h->num_cu * 8, stg::launch_gather_add_batch, s);
         for (size_t i = 0; i < ntasks; ++i) {
             const stg_send_task_t &t = tasks[i];
             const size_t n = t.bucket.n;
@@ -1051,54 +987,41 @@ int stg_merge_send_batch_device(stg_codec_t h, const stg_send_task_t *tasks, siz
             const uint64_t nbk = vec ? std::max<uint64_t>(1, ((n - head) / 4 + stg::SEND_GATHER_TILE / 4 - 1) /
                                                                  (stg::SEND_GATHER_TILE / 4))
                                      : (n + stg::SEND_GATHER_TILE - 1) / stg::SEND_GATHER_TILE;
-            if (gb.nt == stg::SEND_BATCH || (gb.nt && blocks + nbk > cap))
-                if ((rc = flush())) return rc;
-            stg::SendGather &d = gb.t[gb.nt++];
-            d.dst = g.dst;
-            d.resid = g.resid;
-            for (uint32_t r = 1; r < g.nsrc; ++r) d.src[r] = g.src[r];
-            d.n = n;
-            d.nsrc = g.nsrc;
-            d.blk0 = (uint32_t)blocks;
-            d.vec = vec;
-            d.head = (uint32_t)head;
-            blocks += nbk;
+            stg::SendGather *d;
+            if ((rc = gb.add(nbk, &d))) return rc;
+            d->dst = g.dst;
+            d->resid = g.resid;
+            for (uint32_t r = 1; r < g.nsrc; ++r) d->src[r] = g.src[r];
+            d->n = n;
+            d->nsrc = g.nsrc;
+            d->vec = vec;
+            d->head = (uint32_t)head;
         }
-        if ((rc = flush())) return rc;
+        if ((rc = gb.flush())) return rc;
         if ((rc = run_tv16(h, bk.data(), ntasks, s, res.data()))) return rc;
     }
     // finish groups: tail copy, error feedback by the true indices, wire form
-    stg::SendFinishBatch fb{};
-    uint64_t blocks = 0;
-    auto flush = [&]() -> int {
-        if (fb.nt) HIP_TRY(stg::launch_ef_pack_batch(fb, (uint32_t)blocks, s));
-        fb = stg::SendFinishBatch{};
-        blocks = 0;
-        return STG_OK;
-    };
+    auto fb = stream_packer<stg::SendFinishBatch>(GRID_MAX, stg::launch_ef_pack_batch, s);
     for (size_t i = 0; i < ntasks; ++i) {
         const stg_bucket_t &b = tasks[i].bucket;
         if (!b.n) continue;
         const size_t count = std::min<size_t>(b.idx_cap, b.n);  // the pairs the fill writes
         if (!count && !tasks[i].d_residual) continue;
         const uint64_t nbk = std::max<uint64_t>(1, (count + STG_WG - 1) / STG_WG);
-        if (fb.nt == stg::SEND_BATCH || blocks + nbk > 0x7fffffffull)
-            if ((rc = flush())) return rc;
-        stg::SendFinish &d = fb.t[fb.nt++];
-        d.idx = bk[i].d_idx;
-        d.val = bk[i].d_val;
-        d.idx_out = b.d_idx;
-        d.val_out = b.d_val;
-        d.grad = const_cast<float *>(b.d_src);
-        d.resid = tasks[i].d_residual;
-        d.n = b.n;
-        d.count = (uint32_t)count;
-        d.flag = (uint32_t)tasks[i].wire_flag;
-        d.blk0 = (uint32_t)blocks;
-        d.zero0 = b.idx_cap > count;
-        blocks += nbk;
+        stg::SendFinish *d;
+        if ((rc = fb.add(nbk, &d))) return rc;
+        d->idx = bk[i].d_idx;
+        d->val = bk[i].d_val;
+        d->idx_out = b.d_idx;
+        d->val_out = b.d_val;
+        d->grad = const_cast<float *>(b.d_src);
+        d->resid = tasks[i].d_residual;
+        d->n = b.n;
+        d->count = (uint32_t)count;
+        d->flag = (uint32_t)tasks[i].wire_flag;
+        d->zero0 = b.idx_cap > count;
     }
-    return flush();
+    return fb.flush();
 }
 
 int stg_codec_compress_host(stg_codec_t h, const char *key, const float *src, size_t n, uint32_t k,
@@ -1114,24 +1037,22 @@ int stg_codec_compress_host(stg_codec_t h, const char *key, const float *src, si
     if ((rc = h->workspace(s, &ws))) return rc;
     {
         std::lock_guard<std::mutex> g(ws->mu);
-        if ((rc = ws->grow(ws->h_src, ws->cap_src, std::max<size_t>(n, 1)))) return rc;
-        size_t co = ws->cap_out;
-        if ((rc = ws->grow(ws->h_idx, co, std::max<size_t>(idx_cap, 1)))) return rc;
-        co = ws->cap_out;
-        if ((rc = ws->grow(ws->h_val, co, std::max<size_t>(idx_cap, 1)))) return rc;
-        ws->cap_out = co;
-        if (!ws->h_count) HIP_TRY(hipMalloc(&ws->h_count, sizeof(uint32_t)));
+        HIP_TRY(ws->h_src.reserve(std::max<size_t>(n, 1), s, false));
+        HIP_TRY(ws->h_idx.reserve(std::max<size_t>(idx_cap, 1), s, false));
+        HIP_TRY(ws->h_val.reserve(std::max<size_t>(idx_cap, 1), s, false));
+        HIP_TRY(ws->h_count.reserve(1, s, false));
         if (!ws->pinned_count) HIP_TRY(hipHostMalloc(&ws->pinned_count, 2 * sizeof(uint32_t)));
-        if (n) HIP_TRY(hipMemcpyAsync(ws->h_src, src, n * sizeof(float), hipMemcpyHostToDevice, s));
+        if (n) HIP_TRY(hipMemcpyAsync(ws->h_src.get(), src, n * sizeof(float), hipMemcpyHostToDevice, s));
     }
     // threshold-v keys its state by the caller's (host) src pointer
-    rc = run_device(h, key, ws->h_src, src, n, k, ws->h_idx, idx_cap, ws->h_val, idx_cap, idx_offset, ws->h_count, s);
+    rc = run_device(h, key, ws->h_src.get(), src, n, k, ws->h_idx.get(), idx_cap, ws->h_val.get(), idx_cap, idx_offset,
+                    ws->h_count.get(), s);
     if (rc) return rc;
     std::lock_guard<std::mutex> g(ws->mu);
-    HIP_TRY(hipMemcpyAsync(ws->pinned_count, ws->h_count, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(ws->pinned_count, ws->h_count.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     if (idx_cap) {
-        HIP_TRY(hipMemcpyAsync(dst_idx, ws->h_idx, idx_cap * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(dst_val, ws->h_val, std::min(idx_cap, val_cap) * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(dst_idx, ws->h_idx.get(), idx_cap * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(dst_val, ws->h_val.get(), std::min(idx_cap, val_cap) * sizeof(float), hipMemcpyDeviceToHost, s));
     }
     // the workspace's sticky failure word rides along: a device-side failure
     // (a bounded wait that gave up) is an error, never a silent wrong result
@@ -1222,8 +1143,7 @@ int stg_codec_check(stg_codec_t h) {
             return fail(STG_ERR_DEVICE, m);
         }
         // diagnostics (STG_DEBUG_TV16_COUNT): the scan's counters of this workspace
-        static const bool count = getenv("STG_DEBUG_TV16_COUNT") && atoi(getenv("STG_DEBUG_TV16_COUNT")) != 0;
-        if (count) {
+        if (stg::tv16_debug_count()) {
             uint32_t w[5] = {};
             HIP_TRY(hipMemcpy(w, kv.second->d.misc, sizeof w, hipMemcpyDeviceToHost));
             fprintf(stderr, "stg: tv16 scan counters, stream %p: launches %u, dead workgroups %u (most in one launch %u)\n",
@@ -1253,13 +1173,15 @@ int stg_codec_debug_words(stg_codec_t h, void *stream, uint32_t *out, int n) {
 int stg_error_feedback_device(float *d_grad, size_t n, const uint32_t *d_idx, size_t numel, float *d_residual,
                               void *stream) {
     if ((n && (!d_grad || !d_residual)) || (numel && !d_idx)) return fail(STG_ERR_INVALID, "null argument");
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    int ncu = 256;
-    HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+    int ncu;
+    if (const int rc = device_cus(&ncu)) return rc;
     HIP_TRY(stg::launch_error_feedback(d_grad, n, d_idx, numel, d_residual, ncu, static_cast<hipStream_t>(stream)));
     return STG_OK;
 }
+
+}  // extern "C"
+
+namespace {
 
 // One MERGE decompress call: the rank streams as the launcher takes them, built
 // once at the C entry point, and the entry's other arguments.
@@ -1327,10 +1249,10 @@ static int merge_run_locked(const MergeCall &c, MergeScratch *ms, int ncu, const
     int rc = merge_scratch_ensure(ms, s, c.n, c.per_rank, c.world);
     if (rc) return rc;
     if (++ms->tag == 0) ms->tag = 1;
-    const stg::Win1Desc w1{ms->desc, ms->ticket, ms->tag, ms->fail, reinterpret_cast<uint32_t *>(ms->ticket + 1),
-                           sgd, adam};
+    const stg::Win1Desc w1{ms->desc.get(), ms->ticket.get(), ms->tag, ms->fail.get(),
+                           reinterpret_cast<uint32_t *>(ms->ticket.get() + 1), sgd, adam};
     HIP_TRY(stg::launch_scatter_merge(c.rs.data(), c.per_rank, c.world, c.n, c.dense, c.mark, c.out_idx, c.out_val,
-                                      c.out_count, ms->tiles, ms->win, ncu, s, w1));
+                                      c.out_count, ms->tiles.get(), ms->win.get(), ncu, s, w1));
     return STG_OK;
 }
 
@@ -1340,10 +1262,8 @@ static int merge_run_locked(const MergeCall &c, MergeScratch *ms, int ncu, const
 static int merge_run(const MergeCall &c, const stg::SgdLaunch *sgd = nullptr, const stg::AdamLaunch *adam = nullptr) {
     int rc = merge_size_check(c);
     if (rc) return rc;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    int ncu = 256;
-    HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+    int dev, ncu;
+    if ((rc = device_cus(&ncu, &dev))) return rc;
     const std::shared_ptr<MergeScratch> ms = merge_scratch(dev, static_cast<hipStream_t>(c.stream));
     std::lock_guard<std::mutex> g(ms->mu);
     return merge_run_locked(c, ms.get(), ncu, sgd, adam);
@@ -1360,6 +1280,344 @@ static int merge_fused_limits(const MergeCall &c, uint32_t param_len) {
         return fail(STG_ERR_UNSUPPORTED, "more than 2^32-1 elements or an empty parameter");
     return STG_OK;
 }
+
+// A name's buffer of an SGD handle (momentum, last-touched words) read back once
+// the stream's work is done.
+template <typename T>
+static int sgd_read_back(stg_sgd_t o, const std::unordered_map<std::string, stg_sgd::Named<T>> &of, const char *name,
+                         T *host_out, uint32_t len, void *stream, const char *missing) {
+    HIP_TRY(hipSetDevice(o->device));
+    T *b = nullptr;
+    uint32_t n = 0;
+    {
+        std::lock_guard<std::mutex> g(o->mu);
+        auto it = of.find(name);
+        if (it == of.end()) return fail(STG_ERR_INVALID, missing);
+        b = it->second.buf.get();
+        n = it->second.len;
+    }
+    HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    HIP_TRY(hipMemcpy(host_out, b, std::min(len, n) * sizeof(T), hipMemcpyDeviceToHost));
+    return STG_OK;
+}
+
+// ---- the two optimizers' policies ----
+// What SGD and Adam differ in at every entry that steps: the handle's state of a
+// name, whether the step fuses into a world-1 emission, the launch, and the
+// fields a tensor of a batched launch carries.
+struct SgdBatch {
+    using Handle = stg_sgd_t;
+    using Launch = stg::SgdLaunch;
+    static bool fuses(Handle) { return true; }
+    static int refuse(Handle, uint32_t, uint32_t) { return STG_OK; }
+    static uint32_t step_cap(Handle, uint32_t) { return 0xffffffffu; }
+    static bool len_checked(Handle o) { return o->smart; }  // only the last-touched array pins a name's length
+    static int len_check(Handle o, const char *name, uint32_t param_len) {
+        auto it = o->last.find(name);
+        if (it != o->last.end() && it->second.len != param_len)
+            return fail(STG_ERR_INVALID, "param_len differs from the name's first smart-momentum call");
+        return STG_OK;
+    }
+    // One optimize_raw call's launch arguments (the momentum buffer of `name`,
+    // created zeroed on its first call: sgd.cpp:40-47; the iteration count).
+    // Caller holds o->mu.
+    static int prepare_locked(Handle o, const char *name, float *d_param, uint32_t param_len, hipStream_t s,
+                              Launch *out) {
+        bool first = false;
+        float *mom = nullptr;
+        uint32_t *last = nullptr;
+        uint32_t iter;
+        if (o->smart) {  // the reference's array is zero until the option is on (sgd.cpp:46-47, 258-259)
+            auto it = o->last.find(name);
+            if (it == o->last.end()) {
+                stg_sgd::Named<uint32_t> b;
+                HIP_TRY(b.buf.reserve(std::max<size_t>(param_len, 1), s, true));
+                b.len = param_len;
+                it = o->last.emplace(name, std::move(b)).first;
+            }
+            if (it->second.len != param_len)
+                return fail(STG_ERR_INVALID, "param_len differs from the name's first smart-momentum call");
+            last = it->second.buf.get();
+        }
+        iter = o->iter;
+        if (o->momentum != 0.f) {
+            auto it = o->mom.find(name);
+            if (it == o->mom.end()) {  // sgd.cpp:40-47: zeroed buffer, first = true
+                stg_sgd::Named<float> b;
+                HIP_TRY(b.buf.reserve(std::max<size_t>(param_len, 1), s, true));
+                b.len = param_len;
+                it = o->mom.emplace(name, std::move(b)).first;
+                first = true;
+            }
+            mom = it->second.buf.get();
+        }
+        o->iter++;  // sgd.cpp:262
+        stg::SgdLaunch a{};
+        a.param = d_param;
+        a.param_len = param_len;
+        a.mom = mom;
+        a.first = first;
+        a.momentum = o->momentum;
+        a.dampening = o->dampening;
+        a.weight_decay = o->weight_decay;
+        a.lr = o->maximize ? -(double)o->lr : (double)o->lr;  // sgd.cpp:51
+        a.nesterov = o->nesterov;
+        a.last = last;
+        a.iter = iter;
+        a.pow_tab = o->pow_tab.get();
+        a.pow_len = (uint32_t)o->pow_tab.cap();
+        a.fail = o->fail.get();
+        *out = a;
+        return STG_OK;
+    }
+    static hipError_t launch(const Launch &a, hipStream_t s) { return stg::launch_sgd(a, s); }
+    static const stg::SgdLaunch *sgd(const Launch *a) { return a; }
+    static const stg::AdamLaunch *adam(const Launch *) { return nullptr; }
+    static int opt(const Launch &a) { return a.last ? 1 : 0; }
+    static void common(const Launch &a, stg::MergeBatchArgs &w) { w.sgd = a; }
+    static void fill(const Launch &a, stg::MergeTensor &d) {
+        d.s0 = a.mom;
+        d.s1 = a.last;
+        d.u.sgd.iter = a.iter;
+        d.u.sgd.first = a.first;
+    }
+};
+
+struct AdamBatch {
+    using Handle = stg_adam_t;
+    using Launch = stg::AdamLaunch;
+    static bool fuses(Handle o) { return !o->amsgrad; }  // amsgrad is never fused ...
+    static int refuse(Handle o, uint32_t grad_len, uint32_t param_len) {
+        if (o->amsgrad && grad_len > param_len)
+            return fail(STG_ERR_INVALID, "amsgrad: grad_len > param_len (indices must be unique)");
+        return STG_OK;
+    }
+    static uint32_t step_cap(Handle o, uint32_t param_len) { return o->amsgrad ? param_len : 0xffffffffu; }  // ... and caps the step's length
+    static bool len_checked(Handle) { return true; }
+    static int len_check(Handle o, const char *name, uint32_t param_len) {
+        auto it = o->st.find(name);
+        if (it != o->st.end() && it->second.len != param_len)
+            return fail(STG_ERR_INVALID, "param_len differs from the name's first call");
+        return STG_OK;
+    }
+    // One optimize_raw call's launch arguments: the name's state (created zeroed
+    // on its first call: adam.cpp:28-35), its tick and the bias corrections.
+    // Caller holds o->mu.
+    static int prepare_locked(Handle o, const char *name, float *d_param, uint32_t param_len, hipStream_t s,
+                              Launch *out) {
+        stg::AdamLaunch a{};
+        uint32_t tick;
+        HIP_TRY(o->fail.reserve(1, s, true));  // the handle's failure word, allocated with its first state
+        auto it = o->st.find(name);
+        if (it == o->st.end()) {  // adam.cpp:28-35: zeroed m and v, vmax 0, tick 1
+            stg_adam::Name nm;
+            const size_t L = std::max<size_t>(param_len, 1);
+            HIP_TRY(nm.mvv.reserve(2 * L + 1, s, true));
+            if (o->amsgrad)  // one tagged uint64 per tile; zero never matches a tick (>= 1)
+                HIP_TRY(nm.tiles.reserve((L + stg::ADAM_TILE - 1) / stg::ADAM_TILE, s, true));
+            nm.len = param_len;
+            it = o->st.emplace(name, std::move(nm)).first;
+        }
+        if (it->second.len != param_len) return fail(STG_ERR_INVALID, "param_len differs from the name's first call");
+        a.m = it->second.m();
+        a.v = it->second.v();
+        a.vmax = it->second.vmax();
+        a.tiles = reinterpret_cast<uint32_t *>(it->second.tiles.get());
+        tick = it->second.tick++;  // adam.cpp:40,82
+        a.param = d_param;
+        a.param_len = param_len;
+        a.b1 = o->b1;
+        a.b2 = o->b2;
+        a.eps = o->eps;
+        a.weight_decay = o->weight_decay;
+        a.lr = (double)o->lr;
+        a.c1 = 1.0 - std::pow((double)o->b1, (double)tick);  // adam.cpp:42,67
+        a.c2 = 1.0 - std::pow((double)o->b2, (double)tick);  // adam.cpp:43,68
+        a.amsgrad = o->amsgrad;
+        a.maximize = o->maximize;
+        a.tag = tick;
+        a.fail = o->fail.get();
+        *out = a;
+        return STG_OK;
+    }
+    static hipError_t launch(const Launch &a, hipStream_t s) { return stg::launch_adam(a, s); }
+    static const stg::SgdLaunch *sgd(const Launch *) { return nullptr; }
+    static const stg::AdamLaunch *adam(const Launch *a) { return a; }
+    static int opt(const Launch &) { return 2; }
+    static void common(const Launch &a, stg::MergeBatchArgs &w) { w.adam = a; }
+    static void fill(const Launch &a, stg::MergeTensor &d) {
+        d.s0 = a.m;
+        d.s1 = a.v;
+        d.u.adam.c1 = a.c1;
+        d.u.adam.c2 = a.c2;
+    }
+};
+
+// The step of a prepared call over grad_len pairs at most (none: no launch).
+template <class P>
+static int step(typename P::Launch a, const float *d_grad, const uint32_t *d_idx, uint32_t grad_len,
+                const uint32_t *d_grad_len, hipStream_t s) {
+    a.grad = d_grad;
+    a.gidx = d_idx;
+    a.grad_len = grad_len;
+    a.d_grad_len = d_grad_len;
+    if (grad_len) HIP_TRY(P::launch(a, s));
+    return STG_OK;
+}
+
+// ... over a merge's output
+template <class P>
+static int merge_step(typename P::Handle o, const typename P::Launch &a, const MergeCall &c) {
+    const size_t cap = std::min<size_t>(c.per_rank * (size_t)c.world, P::step_cap(o, a.param_len));
+    return step<P>(a, c.out_val, c.out_idx, (uint32_t)cap, c.out_count, static_cast<hipStream_t>(c.stream));
+}
+
+template <class P>
+static int prepare(typename P::Handle o, const char *name, float *d_param, uint32_t param_len, hipStream_t s,
+                   typename P::Launch *out) {
+    std::lock_guard<std::mutex> g(o->mu);
+    return P::prepare_locked(o, name, d_param, param_len, s, out);
+}
+
+// stg_*_optimize_raw_device
+template <class P>
+static int optimize_raw(typename P::Handle o, const char *name, float *d_param, uint32_t param_len,
+                        const float *d_grad, const uint32_t *d_idx, uint32_t grad_len, const uint32_t *d_grad_len,
+                        void *stream) {
+    if (!o || !name) return fail(STG_ERR_INVALID, "null argument");
+    int rc = P::refuse(o, grad_len, param_len);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(o->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    typename P::Launch a;
+    if ((rc = prepare<P>(o, name, d_param, param_len, s, &a))) return rc;
+    return step<P>(a, d_grad, d_idx, grad_len, d_grad_len, s);
+}
+
+// The MERGE decompress `c` over the parameter (c.n == param_len), then the step
+// on its output -- or, where it can be fused, inside its emission.
+template <class P>
+static int merge_optimize(typename P::Handle o, const char *name, float *d_param, uint32_t param_len,
+                          const MergeCall &c) {
+    if (!o || !name) return fail(STG_ERR_INVALID, "null argument");
+    int rc = merge_check(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(o->device));
+    // world 1: the election, then the emission with every winner's step in the
+    // same pass (each index is elected once, so the updates commute).  Otherwise
+    // the merge (of several ranks) first, then the step over its output.
+    const bool fused = c.world == 1 && c.per_rank != 0 && P::fuses(o);
+    if ((rc = fused ? merge_fused_limits(c, param_len) : merge_run(c))) return rc;
+    typename P::Launch a;
+    if ((rc = prepare<P>(o, name, d_param, param_len, static_cast<hipStream_t>(c.stream), &a))) return rc;
+    return fused ? merge_run(c, P::sgd(&a), P::adam(&a)) : merge_step<P>(o, a, c);
+}
+
+// ---- the iteration's ModuleCpuOptimize tasks in one call ----
+template <class P>
+static int merge_optimize_batch(typename P::Handle o, const stg_merge_task_t *tasks, size_t ntasks, void *stream) {
+    if (!o) return fail(STG_ERR_INVALID, "null argument");
+    if (!ntasks) return STG_OK;
+    if (!tasks) return fail(STG_ERR_INVALID, "null task array");
+    const auto refuse = [](size_t i, int rc) {
+        g_err = "task " + std::to_string(i) + ": " + g_err;
+        return rc;
+    };
+    // every check of every task, before any device call or state change
+    std::vector<MergeCall> calls;
+    calls.reserve(ntasks);
+    std::vector<uint8_t> fused(ntasks);
+    for (size_t i = 0; i < ntasks; ++i) {
+        const stg_merge_task_t &t = tasks[i];
+        if (!t.name) return refuse(i, fail(STG_ERR_INVALID, "null name"));
+        calls.push_back(MergeCall{wire_streams(t.ranks, t.world), true, t.per_rank, t.world, t.param_len, t.d_dense,
+                                  t.d_mark, t.d_out_idx, t.d_out_val, t.d_out_count, stream});
+        int rc = merge_check(calls[i]);
+        fused[i] = t.world == 1 && t.per_rank > 0 && P::fuses(o);
+        if (!rc && fused[i]) rc = merge_fused_limits(calls[i], t.param_len);
+        if (!rc) rc = merge_size_check(calls[i]);
+        if (rc) return refuse(i, rc);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::vector<typename P::Launch> L(ntasks);
+    {   // the batch's iterations and ticks, contiguous: task i prepares as the i-th call would
+        std::lock_guard<std::mutex> g(o->mu);
+        if (P::len_checked(o)) {
+            std::unordered_map<std::string, uint32_t> seen;
+            for (size_t i = 0; i < ntasks; ++i) {
+                int rc = P::len_check(o, tasks[i].name, tasks[i].param_len);
+                const auto ins = seen.emplace(tasks[i].name, tasks[i].param_len);
+                if (!rc && ins.first->second != tasks[i].param_len)
+                    rc = fail(STG_ERR_INVALID, "param_len differs from an earlier task of the same name");
+                if (rc) return refuse(i, rc);
+            }
+        }
+        HIP_TRY(hipSetDevice(o->device));
+        for (size_t i = 0; i < ntasks; ++i) {
+            const int rc = P::prepare_locked(o, tasks[i].name, tasks[i].d_param, tasks[i].param_len, s, &L[i]);
+            if (rc) return refuse(i, rc);  // a HIP failure: the tasks before it keep their iterations
+        }
+    }
+    int dev, ncu;
+    if (const int rc = device_cus(&ncu, &dev)) return rc;
+    const std::shared_ptr<MergeScratch> ms = merge_scratch(dev, s);
+    std::lock_guard<std::mutex> g(ms->mu);
+    // the pending launch: tasks [g0, g0 + its count), `sum_n` winner words so far
+    size_t g0 = 0, sum_n = 0;
+    auto pk = stg::make_packer<stg::MergeBatchArgs>(~uint64_t(0), [&](stg::MergeBatchArgs &w, uint32_t blocks) -> int {
+        const int rc = merge_scratch_ensure(ms.get(), s, sum_n, 0, 1, blocks);
+        sum_n = 0;
+        if (rc) return rc;
+        if (++ms->tag == 0) ms->tag = 1;
+        w.tag = ms->tag;
+        w.win = ms->win.get();
+        w.desc = ms->desc.get();
+        w.ctl = ms->bctl.get();
+        w.fail = ms->fail.get();
+        HIP_TRY(stg::launch_merge_batch(w, blocks, P::opt(L[g0]), s));
+        return STG_OK;
+    });
+    for (size_t i = 0; i < ntasks; ++i) {
+        const stg_merge_task_t &t = tasks[i];
+        int rc;
+        if (!fused[i]) {  // the per-tensor sequence at its place in the order
+            if ((rc = pk.flush())) return rc;
+            if ((rc = merge_run_locked(calls[i], ms.get(), ncu, nullptr, nullptr))) return rc;
+            if ((rc = merge_step<P>(o, L[i], calls[i]))) return rc;
+            continue;
+        }
+        // (the packer closes at MERGE_BATCH tensors; the winner-word cap and a repeated name close here)
+        bool close = pk.count() && sum_n + t.param_len > stg::MERGE_BATCH_WIN_CAP;
+        for (size_t q = g0; !close && q < g0 + pk.count(); ++q) close = strcmp(tasks[q].name, t.name) == 0;
+        if (close && (rc = pk.flush())) return rc;
+        stg::MergeTensor *dp;
+        if ((rc = pk.add((t.per_rank + stg::MERGE_BATCH_TILE - 1) / stg::MERGE_BATCH_TILE, &dp))) return rc;
+        if (pk.count() == 1) {
+            g0 = i;
+            P::common(L[i], pk.table());
+        }
+        stg::MergeTensor &d = *dp;
+        const stg::RankStream &k = calls[i].rs[0];
+        d.idx = k.idx;
+        d.val = k.val;
+        d.flag = k.flag;
+        d.out_idx = t.d_out_idx;
+        d.out_val = t.d_out_val;
+        d.out_count = t.d_out_count;
+        d.param = t.d_param;
+        d.m = (uint32_t)t.per_rank;
+        d.n = t.param_len;
+        d.win0 = (uint32_t)sum_n;
+        d.desc0 = d.blk0;
+        P::fill(L[i], d);
+        sum_n += t.param_len;
+    }
+    return pk.flush();
+}
+
+}  // namespace
+
+extern "C" {
 
 int stg_scatter_merge_device(const uint32_t *d_idx, const float *d_val, size_t per_rank, int world, size_t n,
                              float *d_dense, uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
@@ -1389,7 +1647,7 @@ int stg_scatter_merge_check(void *stream) {
     std::lock_guard<std::mutex> g(ms->mu);
     HIP_TRY(hipStreamSynchronize(s));
     uint32_t f = 0;
-    if (ms->fail) HIP_TRY(hipMemcpy(&f, ms->fail, sizeof f, hipMemcpyDeviceToHost));
+    if (ms->fail.get()) HIP_TRY(hipMemcpy(&f, ms->fail.get(), sizeof f, hipMemcpyDeviceToHost));
     if (f) {
         char b[96];
         snprintf(b, sizeof b, "MERGE decompress device failure flags 0x%x (a look-back gave up)", f);
@@ -1438,110 +1696,17 @@ int stg_sgd_destroy(stg_sgd_t o) {
     return STG_OK;
 }
 
-// One optimize_raw call's launch arguments (the momentum buffer of `name`,
-// created zeroed on its first call: sgd.cpp:40-47; the iteration count).
-// Caller holds o->mu.
-static int sgd_prepare_locked(stg_sgd_t o, const char *name, float *d_param, uint32_t param_len, hipStream_t s,
-                              stg::SgdLaunch *out) {
-    bool first = false;
-    float *mom = nullptr;
-    uint32_t *last = nullptr;
-    uint32_t iter;
-    if (o->smart) {  // the reference's array is zero until the option is on (sgd.cpp:46-47, 258-259)
-        auto it = o->last.find(name);
-        if (it == o->last.end()) {
-            uint32_t *b = nullptr;
-            HIP_TRY(hipMalloc(&b, std::max<size_t>(param_len, 1) * sizeof(uint32_t)));
-            HIP_TRY(hipMemsetAsync(b, 0, std::max<size_t>(param_len, 1) * sizeof(uint32_t), s));
-            it = o->last.emplace(name, std::make_pair(b, param_len)).first;
-        }
-        if (it->second.second != param_len)
-            return fail(STG_ERR_INVALID, "param_len differs from the name's first smart-momentum call");
-        last = it->second.first;
-    }
-    iter = o->iter;
-    if (o->momentum != 0.f) {
-        auto it = o->mom.find(name);
-        if (it == o->mom.end()) {  // sgd.cpp:40-47: zeroed buffer, first = true
-            float *b = nullptr;
-            HIP_TRY(hipMalloc(&b, std::max<size_t>(param_len, 1) * sizeof(float)));
-            HIP_TRY(hipMemsetAsync(b, 0, std::max<size_t>(param_len, 1) * sizeof(float), s));
-            o->mom.emplace(name, std::make_pair(b, param_len));
-            mom = b;
-            first = true;
-        } else {
-            mom = it->second.first;
-        }
-    }
-    o->iter++;  // sgd.cpp:262
-    stg::SgdLaunch a{};
-    a.param = d_param;
-    a.param_len = param_len;
-    a.mom = mom;
-    a.first = first;
-    a.momentum = o->momentum;
-    a.dampening = o->dampening;
-    a.weight_decay = o->weight_decay;
-    a.lr = o->maximize ? -(double)o->lr : (double)o->lr;  // sgd.cpp:51
-    a.nesterov = o->nesterov;
-    a.last = last;
-    a.iter = iter;
-    a.pow_tab = o->pow_tab;
-    a.pow_len = o->pow_len;
-    a.fail = o->fail;
-    *out = a;
-    return STG_OK;
-}
-
-static int sgd_prepare(stg_sgd_t o, const char *name, float *d_param, uint32_t param_len, hipStream_t s,
-                       stg::SgdLaunch *out) {
-    std::lock_guard<std::mutex> g(o->mu);
-    return sgd_prepare_locked(o, name, d_param, param_len, s, out);
-}
-
 int stg_sgd_optimize_raw_device(stg_sgd_t o, const char *name, float *d_param, uint32_t param_len, const float *d_grad,
                                 const uint32_t *d_idx, uint32_t grad_len, const uint32_t *d_grad_len, void *stream) {
-    if (!o || !name) return fail(STG_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(o->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    stg::SgdLaunch a;
-    int rc = sgd_prepare(o, name, d_param, param_len, s, &a);
-    if (rc) return rc;
-    a.grad = d_grad;
-    a.gidx = d_idx;
-    a.grad_len = grad_len;
-    a.d_grad_len = d_grad_len;
-    if (grad_len) HIP_TRY(stg::launch_sgd(a, s));
-    return STG_OK;
-}
-
-// The MERGE decompress `c` over the parameter (c.n == param_len), then the step
-// on its output -- or, where it can be fused, inside its emission.
-static int merge_optimize_sgd(stg_sgd_t o, const char *name, float *d_param, uint32_t param_len, const MergeCall &c) {
-    if (!o || !name) return fail(STG_ERR_INVALID, "null argument");
-    int rc = merge_check(c);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(o->device));
-    if (c.world != 1 || c.per_rank == 0) {  // the merge of several ranks, then the step over its output
-        if ((rc = merge_run(c))) return rc;
-        const size_t cap = c.per_rank * (size_t)c.world;
-        return stg_sgd_optimize_raw_device(o, name, d_param, param_len, c.out_val, c.out_idx,
-                                           (uint32_t)std::min<size_t>(cap, 0xffffffffu), c.out_count, c.stream);
-    }
-    // world 1: the election, then the emission with every winner's step in the
-    // same pass (each index is elected once, so the updates commute)
-    if ((rc = merge_fused_limits(c, param_len))) return rc;
-    stg::SgdLaunch a;
-    if ((rc = sgd_prepare(o, name, d_param, param_len, static_cast<hipStream_t>(c.stream), &a))) return rc;
-    return merge_run(c, &a, nullptr);
+    return optimize_raw<SgdBatch>(o, name, d_param, param_len, d_grad, d_idx, grad_len, d_grad_len, stream);
 }
 
 int stg_merge_optimize_sgd_device(stg_sgd_t o, const char *name, float *d_param, uint32_t param_len,
                                   const uint32_t *d_idx, const float *d_val, size_t per_rank, int world,
                                   float *d_dense, uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
                                   uint32_t *d_out_count, void *stream) {
-    return merge_optimize_sgd(o, name, d_param, param_len,
-                              MergeCall{decoded_streams(d_idx, d_val, per_rank, world), false, per_rank, world,
+    return merge_optimize<SgdBatch>(o, name, d_param, param_len,
+                                    MergeCall{decoded_streams(d_idx, d_val, per_rank, world), false, per_rank, world,
                                         param_len, d_dense, d_mark, d_out_idx, d_out_val, d_out_count, stream});
 }
 
@@ -1549,26 +1714,14 @@ int stg_merge_optimize_sgd_wire_device(stg_sgd_t o, const char *name, float *d_p
                                        const stg_rank_stream_t *ranks, size_t per_rank, int world, float *d_dense,
                                        uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
                                        uint32_t *d_out_count, void *stream) {
-    return merge_optimize_sgd(o, name, d_param, param_len,
-                              MergeCall{wire_streams(ranks, world), true, per_rank, world, param_len, d_dense, d_mark,
+    return merge_optimize<SgdBatch>(o, name, d_param, param_len,
+                                    MergeCall{wire_streams(ranks, world), true, per_rank, world, param_len, d_dense, d_mark,
                                         d_out_idx, d_out_val, d_out_count, stream});
 }
 
 int stg_sgd_get_momentum(stg_sgd_t o, const char *name, float *host_out, uint32_t len, void *stream) {
     if (!o || !name) return fail(STG_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(o->device));
-    float *b = nullptr;
-    uint32_t n = 0;
-    {
-        std::lock_guard<std::mutex> g(o->mu);
-        auto it = o->mom.find(name);
-        if (it == o->mom.end()) return fail(STG_ERR_INVALID, "no momentum buffer for this name");
-        b = it->second.first;
-        n = it->second.second;
-    }
-    HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    HIP_TRY(hipMemcpy(host_out, b, std::min(len, n) * sizeof(float), hipMemcpyDeviceToHost));
-    return STG_OK;
+    return sgd_read_back(o, o->mom, name, host_out, len, stream, "no momentum buffer for this name");
 }
 
 // The factor table of smart momentum: (float)pow((double)m, (double)d) by the
@@ -1588,7 +1741,7 @@ int stg_sgd_set_smart_momentum(stg_sgd_t o, int on) {
     if (!(o->momentum > 0.f && o->momentum < 1.f))
         return fail(STG_ERR_INVALID, "smart momentum needs 0 < momentum < 1");
     std::lock_guard<std::mutex> g(o->mu);
-    if (!o->pow_tab) {
+    if (!o->pow_tab.get()) {
         std::vector<float> tab;
         for (;;) {
             const float v = (float)std::pow((double)o->momentum, (double)tab.size());
@@ -1598,20 +1751,15 @@ int stg_sgd_set_smart_momentum(stg_sgd_t o, int on) {
                 return fail(STG_ERR_UNSUPPORTED, "smart momentum: the factor table of this momentum exceeds 2^22 entries");
         }
         HIP_TRY(hipSetDevice(o->device));
-        float *t = nullptr;
-        uint32_t *f = nullptr;
-        HIP_TRY(hipMalloc(&t, tab.size() * sizeof(float)));
-        if (hipMemcpy(t, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMalloc(&f, sizeof(uint32_t)) != hipSuccess || hipMemset(f, 0, sizeof(uint32_t)) != hipSuccess ||
-            hipDeviceSynchronize() != hipSuccess) {
-            (void)hipFree(t);
-            (void)hipFree(f);
+        stg::DevBuf<float> t;  // (exactly tab.size() entries: its capacity is the table's length)
+        stg::DevBuf<uint32_t> f;
+        HIP_TRY(t.reserve(tab.size(), nullptr, false));
+        if (hipMemcpy(t.get(), tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+            f.reserve(1, nullptr, true) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
             return fail(STG_ERR_HIP, "smart momentum: uploading the factor table failed");
-        }
         // resident before any launch can name it; never moved or freed before destroy
-        o->pow_tab = t;
-        o->pow_len = (uint32_t)tab.size();
-        o->fail = f;
+        o->pow_tab = std::move(t);
+        o->fail = std::move(f);
     }
     o->smart = true;
     return STG_OK;
@@ -1619,19 +1767,7 @@ int stg_sgd_set_smart_momentum(stg_sgd_t o, int on) {
 
 int stg_sgd_get_last(stg_sgd_t o, const char *name, uint32_t *host_out, uint32_t len, void *stream) {
     if (!o || !name || (len && !host_out)) return fail(STG_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(o->device));
-    uint32_t *b = nullptr;
-    uint32_t n = 0;
-    {
-        std::lock_guard<std::mutex> g(o->mu);
-        auto it = o->last.find(name);
-        if (it == o->last.end()) return fail(STG_ERR_INVALID, "no smart-momentum state for this name");
-        b = it->second.first;
-        n = it->second.second;
-    }
-    HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    HIP_TRY(hipMemcpy(host_out, b, std::min(len, n) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return STG_OK;
+    return sgd_read_back(o, o->last, name, host_out, len, stream, "no smart-momentum state for this name");
 }
 
 int stg_sgd_get_iter(stg_sgd_t o, uint32_t *out) {
@@ -1646,7 +1782,7 @@ int stg_sgd_check(stg_sgd_t o, void *stream) {
     uint32_t *fw = nullptr;
     {
         std::lock_guard<std::mutex> g(o->mu);
-        fw = o->fail;
+        fw = o->fail.get();
     }
     if (!fw) return STG_OK;  // the option was never on: nothing can have failed
     HIP_TRY(hipSetDevice(o->device));
@@ -1680,108 +1816,18 @@ int stg_adam_destroy(stg_adam_t o) {
     return STG_OK;
 }
 
-// One optimize_raw call's launch arguments: the name's state (created zeroed
-// on its first call: adam.cpp:28-35), its tick and the bias corrections.
-// Caller holds o->mu.
-static int adam_prepare_locked(stg_adam_t o, const char *name, float *d_param, uint32_t param_len, hipStream_t s,
-                               stg::AdamLaunch *out) {
-    stg::AdamLaunch a{};
-    uint32_t tick;
-    if (!o->fail) {  // the handle's failure word, allocated with its first state
-        HIP_TRY(hipMalloc(&o->fail, sizeof(uint32_t)));
-        HIP_TRY(hipMemsetAsync(o->fail, 0, sizeof(uint32_t), s));
-    }
-    auto it = o->st.find(name);
-    if (it == o->st.end()) {  // adam.cpp:28-35: zeroed m and v, vmax 0, tick 1
-        stg_adam::Name nm;
-        const size_t L = std::max<size_t>(param_len, 1);
-        // one allocation: m | v | vmax
-        HIP_TRY(hipMalloc(&nm.m, (2 * L + 1) * sizeof(float)));
-        HIP_TRY(hipMemsetAsync(nm.m, 0, (2 * L + 1) * sizeof(float), s));
-        nm.v = nm.m + L;
-        nm.vmax = nm.m + 2 * L;
-        if (o->amsgrad) {  // one tagged uint64 per tile; zero never matches a tick (>= 1)
-            const size_t nt = (L + stg::ADAM_TILE - 1) / stg::ADAM_TILE;
-            HIP_TRY(hipMalloc(&nm.tiles, nt * sizeof(uint64_t)));
-            HIP_TRY(hipMemsetAsync(nm.tiles, 0, nt * sizeof(uint64_t), s));
-        }
-        nm.len = param_len;
-        it = o->st.emplace(name, nm).first;
-    }
-    if (it->second.len != param_len) return fail(STG_ERR_INVALID, "param_len differs from the name's first call");
-    a.m = it->second.m;
-    a.v = it->second.v;
-    a.vmax = it->second.vmax;
-    a.tiles = it->second.tiles;
-    tick = it->second.tick++;  // adam.cpp:40,82
-    a.param = d_param;
-    a.param_len = param_len;
-    a.b1 = o->b1;
-    a.b2 = o->b2;
-    a.eps = o->eps;
-    a.weight_decay = o->weight_decay;
-    a.lr = (double)o->lr;
-    a.c1 = 1.0 - std::pow((double)o->b1, (double)tick);  // adam.cpp:42,67
-    a.c2 = 1.0 - std::pow((double)o->b2, (double)tick);  // adam.cpp:43,68
-    a.amsgrad = o->amsgrad;
-    a.maximize = o->maximize;
-    a.tag = tick;
-    a.fail = o->fail;
-    *out = a;
-    return STG_OK;
-}
-
-static int adam_prepare(stg_adam_t o, const char *name, float *d_param, uint32_t param_len, hipStream_t s,
-                        stg::AdamLaunch *out) {
-    std::lock_guard<std::mutex> g(o->mu);
-    return adam_prepare_locked(o, name, d_param, param_len, s, out);
-}
-
 int stg_adam_optimize_raw_device(stg_adam_t o, const char *name, float *d_param, uint32_t param_len,
                                  const float *d_grad, const uint32_t *d_idx, uint32_t grad_len,
                                  const uint32_t *d_grad_len, void *stream) {
-    if (!o || !name) return fail(STG_ERR_INVALID, "null argument");
-    if (o->amsgrad && grad_len > param_len)
-        return fail(STG_ERR_INVALID, "amsgrad: grad_len > param_len (indices must be unique)");
-    HIP_TRY(hipSetDevice(o->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    stg::AdamLaunch a;
-    int rc = adam_prepare(o, name, d_param, param_len, s, &a);
-    if (rc) return rc;
-    a.grad = d_grad;
-    a.gidx = d_idx;
-    a.grad_len = grad_len;
-    a.d_grad_len = d_grad_len;
-    if (grad_len) HIP_TRY(stg::launch_adam(a, s));
-    return STG_OK;
-}
-
-// merge_optimize_sgd's twin: amsgrad is never fused, and caps the step's length.
-static int merge_optimize_adam(stg_adam_t o, const char *name, float *d_param, uint32_t param_len,
-                               const MergeCall &c) {
-    if (!o || !name) return fail(STG_ERR_INVALID, "null argument");
-    int rc = merge_check(c);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(o->device));
-    if (c.world != 1 || c.per_rank == 0 || o->amsgrad) {  // the merge, then the step over its output
-        if ((rc = merge_run(c))) return rc;
-        const size_t cap = std::min<size_t>(c.per_rank * (size_t)c.world, o->amsgrad ? param_len : 0xffffffffu);
-        return stg_adam_optimize_raw_device(o, name, d_param, param_len, c.out_val, c.out_idx, (uint32_t)cap,
-                                            c.out_count, c.stream);
-    }
-    // world 1 without amsgrad: the step inside the emission
-    if ((rc = merge_fused_limits(c, param_len))) return rc;
-    stg::AdamLaunch a;
-    if ((rc = adam_prepare(o, name, d_param, param_len, static_cast<hipStream_t>(c.stream), &a))) return rc;
-    return merge_run(c, nullptr, &a);
+    return optimize_raw<AdamBatch>(o, name, d_param, param_len, d_grad, d_idx, grad_len, d_grad_len, stream);
 }
 
 int stg_merge_optimize_adam_device(stg_adam_t o, const char *name, float *d_param, uint32_t param_len,
                                    const uint32_t *d_idx, const float *d_val, size_t per_rank, int world,
                                    float *d_dense, uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
                                    uint32_t *d_out_count, void *stream) {
-    return merge_optimize_adam(o, name, d_param, param_len,
-                               MergeCall{decoded_streams(d_idx, d_val, per_rank, world), false, per_rank, world,
+    return merge_optimize<AdamBatch>(o, name, d_param, param_len,
+                                     MergeCall{decoded_streams(d_idx, d_val, per_rank, world), false, per_rank, world,
                                          param_len, d_dense, d_mark, d_out_idx, d_out_val, d_out_count, stream});
 }
 
@@ -1789,187 +1835,10 @@ int stg_merge_optimize_adam_wire_device(stg_adam_t o, const char *name, float *d
                                         const stg_rank_stream_t *ranks, size_t per_rank, int world, float *d_dense,
                                         uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
                                         uint32_t *d_out_count, void *stream) {
-    return merge_optimize_adam(o, name, d_param, param_len,
-                               MergeCall{wire_streams(ranks, world), true, per_rank, world, param_len, d_dense, d_mark,
+    return merge_optimize<AdamBatch>(o, name, d_param, param_len,
+                                     MergeCall{wire_streams(ranks, world), true, per_rank, world, param_len, d_dense, d_mark,
                                          d_out_idx, d_out_val, d_out_count, stream});
 }
-
-// ---- the iteration's ModuleCpuOptimize tasks in one call ----
-// What the two optimizers' batched entries differ in: whether the step fuses,
-// the name's state, and the fields a tensor of a batched launch carries.
-extern "C++" {
-struct SgdBatch {
-    using Handle = stg_sgd_t;
-    using Launch = stg::SgdLaunch;
-    static bool fuses(Handle) { return true; }
-    static bool len_checked(Handle o) { return o->smart; }  // only the last-touched array pins a name's length
-    static int len_check(Handle o, const char *name, uint32_t param_len) {
-        auto it = o->last.find(name);
-        if (it != o->last.end() && it->second.second != param_len)
-            return fail(STG_ERR_INVALID, "param_len differs from the name's first smart-momentum call");
-        return STG_OK;
-    }
-    static int prepare_locked(Handle o, const stg_merge_task_t &t, hipStream_t s, Launch *out) {
-        return sgd_prepare_locked(o, t.name, t.d_param, t.param_len, s, out);
-    }
-    static int opt(const Launch &a) { return a.last ? 1 : 0; }
-    static void common(const Launch &a, stg::MergeBatchArgs &w) { w.sgd = a; }
-    static void fill(const Launch &a, stg::MergeTensor &d) {
-        d.s0 = a.mom;
-        d.s1 = a.last;
-        d.u.sgd.iter = a.iter;
-        d.u.sgd.first = a.first;
-    }
-    // the step over a merge's output (stg_sgd_optimize_raw_device after its prepare)
-    static int step(Handle, Launch a, const MergeCall &c, hipStream_t s) {
-        a.grad = c.out_val;
-        a.gidx = c.out_idx;
-        a.grad_len = (uint32_t)std::min<size_t>(c.per_rank * (size_t)c.world, 0xffffffffu);
-        a.d_grad_len = c.out_count;
-        if (a.grad_len) HIP_TRY(stg::launch_sgd(a, s));
-        return STG_OK;
-    }
-};
-
-struct AdamBatch {
-    using Handle = stg_adam_t;
-    using Launch = stg::AdamLaunch;
-    static bool fuses(Handle o) { return !o->amsgrad; }
-    static bool len_checked(Handle) { return true; }
-    static int len_check(Handle o, const char *name, uint32_t param_len) {
-        auto it = o->st.find(name);
-        if (it != o->st.end() && it->second.len != param_len)
-            return fail(STG_ERR_INVALID, "param_len differs from the name's first call");
-        return STG_OK;
-    }
-    static int prepare_locked(Handle o, const stg_merge_task_t &t, hipStream_t s, Launch *out) {
-        return adam_prepare_locked(o, t.name, t.d_param, t.param_len, s, out);
-    }
-    static int opt(const Launch &) { return 2; }
-    static void common(const Launch &a, stg::MergeBatchArgs &w) { w.adam = a; }
-    static void fill(const Launch &a, stg::MergeTensor &d) {
-        d.s0 = a.m;
-        d.s1 = a.v;
-        d.u.adam.c1 = a.c1;
-        d.u.adam.c2 = a.c2;
-    }
-    static int step(Handle o, Launch a, const MergeCall &c, hipStream_t s) {
-        a.grad = c.out_val;
-        a.gidx = c.out_idx;
-        a.grad_len = (uint32_t)std::min<size_t>(c.per_rank * (size_t)c.world, o->amsgrad ? a.param_len : 0xffffffffu);
-        a.d_grad_len = c.out_count;
-        if (a.grad_len) HIP_TRY(stg::launch_adam(a, s));
-        return STG_OK;
-    }
-};
-
-template <class P>
-static int merge_optimize_batch(typename P::Handle o, const stg_merge_task_t *tasks, size_t ntasks, void *stream) {
-    if (!o) return fail(STG_ERR_INVALID, "null argument");
-    if (!ntasks) return STG_OK;
-    if (!tasks) return fail(STG_ERR_INVALID, "null task array");
-    const auto refuse = [](size_t i, int rc) {
-        g_err = "task " + std::to_string(i) + ": " + g_err;
-        return rc;
-    };
-    // every check of every task, before any device call or state change
-    std::vector<MergeCall> calls;
-    calls.reserve(ntasks);
-    std::vector<uint8_t> fused(ntasks);
-    for (size_t i = 0; i < ntasks; ++i) {
-        const stg_merge_task_t &t = tasks[i];
-        if (!t.name) return refuse(i, fail(STG_ERR_INVALID, "null name"));
-        calls.push_back(MergeCall{wire_streams(t.ranks, t.world), true, t.per_rank, t.world, t.param_len, t.d_dense,
-                                  t.d_mark, t.d_out_idx, t.d_out_val, t.d_out_count, stream});
-        int rc = merge_check(calls[i]);
-        fused[i] = t.world == 1 && t.per_rank > 0 && P::fuses(o);
-        if (!rc && fused[i]) rc = merge_fused_limits(calls[i], t.param_len);
-        if (!rc) rc = merge_size_check(calls[i]);
-        if (rc) return refuse(i, rc);
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    std::vector<typename P::Launch> L(ntasks);
-    {   // the batch's iterations and ticks, contiguous: task i prepares as the i-th call would
-        std::lock_guard<std::mutex> g(o->mu);
-        if (P::len_checked(o)) {
-            std::unordered_map<std::string, uint32_t> seen;
-            for (size_t i = 0; i < ntasks; ++i) {
-                int rc = P::len_check(o, tasks[i].name, tasks[i].param_len);
-                const auto ins = seen.emplace(tasks[i].name, tasks[i].param_len);
-                if (!rc && ins.first->second != tasks[i].param_len)
-                    rc = fail(STG_ERR_INVALID, "param_len differs from an earlier task of the same name");
-                if (rc) return refuse(i, rc);
-            }
-        }
-        HIP_TRY(hipSetDevice(o->device));
-        for (size_t i = 0; i < ntasks; ++i) {
-            const int rc = P::prepare_locked(o, tasks[i], s, &L[i]);
-            if (rc) return refuse(i, rc);  // a HIP failure: the tasks before it keep their iterations
-        }
-    }
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    int ncu = 256;
-    HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    const std::shared_ptr<MergeScratch> ms = merge_scratch(dev, s);
-    std::lock_guard<std::mutex> g(ms->mu);
-    // the pending launch: tasks [g0, g0 + w.nt), `blocks` tiles and `sum_n` winner words so far
-    stg::MergeBatchArgs w{};
-    size_t g0 = 0, sum_n = 0;
-    uint32_t blocks = 0;
-    const auto flush = [&]() -> int {
-        if (!w.nt) return STG_OK;
-        const int rc = merge_scratch_ensure(ms.get(), s, sum_n, 0, 1, blocks);
-        if (rc) return rc;
-        if (++ms->tag == 0) ms->tag = 1;
-        w.tag = ms->tag;
-        w.win = ms->win;
-        w.desc = ms->desc;
-        w.ctl = ms->bctl;
-        w.fail = ms->fail;
-        HIP_TRY(stg::launch_merge_batch(w, blocks, P::opt(L[g0]), s));
-        w.nt = 0;
-        sum_n = 0;
-        blocks = 0;
-        return STG_OK;
-    };
-    for (size_t i = 0; i < ntasks; ++i) {
-        const stg_merge_task_t &t = tasks[i];
-        int rc;
-        if (!fused[i]) {  // the per-tensor sequence at its place in the order
-            if ((rc = flush())) return rc;
-            if ((rc = merge_run_locked(calls[i], ms.get(), ncu, nullptr, nullptr))) return rc;
-            if ((rc = P::step(o, L[i], calls[i], s))) return rc;
-            continue;
-        }
-        bool close = w.nt == stg::MERGE_BATCH || (w.nt && sum_n + t.param_len > stg::MERGE_BATCH_WIN_CAP);
-        for (size_t q = g0; !close && q < g0 + w.nt; ++q) close = strcmp(tasks[q].name, t.name) == 0;
-        if (close && (rc = flush())) return rc;
-        if (!w.nt) {
-            g0 = i;
-            P::common(L[i], w);
-        }
-        stg::MergeTensor &d = w.t[w.nt++];
-        const stg::RankStream &k = calls[i].rs[0];
-        d.idx = k.idx;
-        d.val = k.val;
-        d.flag = k.flag;
-        d.out_idx = t.d_out_idx;
-        d.out_val = t.d_out_val;
-        d.out_count = t.d_out_count;
-        d.param = t.d_param;
-        d.m = (uint32_t)t.per_rank;
-        d.n = t.param_len;
-        d.blk0 = blocks;
-        d.win0 = (uint32_t)sum_n;
-        d.desc0 = blocks;
-        P::fill(L[i], d);
-        blocks += (uint32_t)((t.per_rank + stg::MERGE_BATCH_TILE - 1) / stg::MERGE_BATCH_TILE);
-        sum_n += t.param_len;
-    }
-    return flush();
-}
-}  // extern "C++"
 
 int stg_merge_optimize_sgd_batch_device(stg_sgd_t o, const stg_merge_task_t *tasks, size_t ntasks, void *stream) {
     return merge_optimize_batch<SgdBatch>(o, tasks, ntasks, stream);
@@ -1982,20 +1851,22 @@ int stg_merge_optimize_adam_batch_device(stg_adam_t o, const stg_merge_task_t *t
 int stg_adam_get_state(stg_adam_t o, const char *name, float *host_m, float *host_v, uint32_t len,
                        float *host_vmax, uint32_t *tick_out, void *stream) {
     if (!o || !name) return fail(STG_ERR_INVALID, "null argument");
-    stg_adam::Name nm;
+    const stg_adam::Name *nm;  // (a name's state never moves or goes before destroy)
+    uint32_t tick;
     {
         std::lock_guard<std::mutex> g(o->mu);
         auto it = o->st.find(name);
         if (it == o->st.end()) return fail(STG_ERR_INVALID, "no Adam state for this name");
-        nm = it->second;
+        nm = &it->second;
+        tick = nm->tick;
     }
     HIP_TRY(hipSetDevice(o->device));
     HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    const size_t c = std::min(len, nm.len);
-    if (host_m) HIP_TRY(hipMemcpy(host_m, nm.m, c * sizeof(float), hipMemcpyDeviceToHost));
-    if (host_v) HIP_TRY(hipMemcpy(host_v, nm.v, c * sizeof(float), hipMemcpyDeviceToHost));
-    if (host_vmax) HIP_TRY(hipMemcpy(host_vmax, nm.vmax, sizeof(float), hipMemcpyDeviceToHost));
-    if (tick_out) *tick_out = nm.tick;
+    const size_t c = std::min(len, nm->len);
+    if (host_m) HIP_TRY(hipMemcpy(host_m, nm->m(), c * sizeof(float), hipMemcpyDeviceToHost));
+    if (host_v) HIP_TRY(hipMemcpy(host_v, nm->v(), c * sizeof(float), hipMemcpyDeviceToHost));
+    if (host_vmax) HIP_TRY(hipMemcpy(host_vmax, nm->vmax(), sizeof(float), hipMemcpyDeviceToHost));
+    if (tick_out) *tick_out = tick;
     return STG_OK;
 }
 
@@ -2004,7 +1875,7 @@ int stg_adam_check(stg_adam_t o, void *stream) {
     HIP_TRY(hipSetDevice(o->device));
     HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     uint32_t f = 0;
-    if (o->fail) HIP_TRY(hipMemcpy(&f, o->fail, sizeof f, hipMemcpyDeviceToHost));
+    if (o->fail.get()) HIP_TRY(hipMemcpy(&f, o->fail.get(), sizeof f, hipMemcpyDeviceToHost));
     if (f) return fail(STG_ERR_DEVICE, "adam: amsgrad look-back timed out (a predecessor tile never published)");
     return STG_OK;
 }
@@ -2025,17 +1896,11 @@ int stg_gather_add_device(float *d_grad0, const float *d_residual, const float *
     if (rc) return rc;
     if (a == b) return STG_OK;
     if (!d_grad0 || (num_gpus > 1 && !d_grads)) return fail(STG_ERR_INVALID, "null argument");
-    stg::GatherArgs g{};
-    g.dst = d_grad0;
-    g.resid = d_residual;
-    g.nsrc = (uint32_t)num_gpus;
-    for (int i = 1; i < num_gpus; ++i) {
+    for (int i = 1; i < num_gpus; ++i)
         if (!d_grads[i]) return fail(STG_ERR_INVALID, "null source");
-        g.src[i] = d_grads[i];
-    }
-    int dev = 0, ncu = 256;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+    const stg::GatherArgs g = gather_args(d_grad0, d_residual, d_grads, num_gpus);
+    int ncu;
+    if (const int rc = device_cus(&ncu)) return rc;
     HIP_TRY(stg::launch_gather_add(g, a, b, ncu, static_cast<hipStream_t>(stream)));
     return STG_OK;
 }
@@ -2049,9 +1914,8 @@ int stg_wire_encode_device(const uint32_t *d_idx, const float *d_val, size_t num
     if (flag & ~(STG_WIRE_U16_IDX | STG_WIRE_F16_VAL)) return fail(STG_ERR_INVALID, "unknown wire flag bits");
     if (!numel) return STG_OK;
     if (!d_idx || !d_val || !d_idx_out || !d_val_out) return fail(STG_ERR_INVALID, "null argument");
-    int dev = 0, ncu = 256;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+    int ncu;
+    if (const int rc = device_cus(&ncu)) return rc;
     HIP_TRY(stg::launch_wire_encode(d_idx, d_val, numel, (uint32_t)flag, d_idx_out, d_val_out, ncu,
                                     static_cast<hipStream_t>(stream)));
     return STG_OK;
@@ -2067,33 +1931,21 @@ int stg_wire_encode_batch_device(const stg_wire_stream_t *streams, size_t nstrea
         if (w.numel > (size_t)STG_WG * 0xffffffull) return fail(STG_ERR_UNSUPPORTED, "wire stream too long for a batch");
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    stg::WireBatch b{};
-    uint64_t blocks = 0;
-    auto flush = [&]() -> int {
-        if (b.nb) HIP_TRY(stg::launch_wire_encode_batch(b, (uint32_t)blocks, s));
-        b = stg::WireBatch{};
-        blocks = 0;
-        return STG_OK;
-    };
+    auto b = stream_packer<stg::WireBatch>(GRID_MAX, stg::launch_wire_encode_batch, s);
     for (size_t i = 0; i < nstreams; ++i) {
         const stg_wire_stream_t &w = streams[i];
         if (!w.numel) continue;
         const uint64_t nbk = (w.numel + STG_WG - 1) / STG_WG;
-        if (b.nb == stg::WIRE_BATCH || blocks + nbk > 0x7fffffffull) {
-            int rc = flush();
-            if (rc) return rc;
-        }
-        stg::WireBucket &d = b.b[b.nb++];
-        d.idx = w.d_idx;
-        d.val = w.d_val;
-        d.idx_out = w.d_idx_out;
-        d.val_out = w.d_val_out;
-        d.n = w.numel;
-        d.flag = (uint32_t)w.flag;
-        d.blk0 = (uint32_t)blocks;
-        blocks += nbk;
+        stg::WireBucket *d;
+        if (const int rc = b.add(nbk, &d)) return rc;
+        d->idx = w.d_idx;
+        d->val = w.d_val;
+        d->idx_out = w.d_idx_out;
+        d->val_out = w.d_val_out;
+        d->n = w.numel;
+        d->flag = (uint32_t)w.flag;
     }
-    return flush();
+    return b.flush();
 }
 
 int stg_wire_decode_device(const void *d_idx_in, const void *d_val_in, size_t numel, int flag, uint32_t *d_idx,
@@ -2101,9 +1953,8 @@ int stg_wire_decode_device(const void *d_idx_in, const void *d_val_in, size_t nu
     if (flag & ~(STG_WIRE_U16_IDX | STG_WIRE_F16_VAL)) return fail(STG_ERR_INVALID, "unknown wire flag bits");
     if (!numel) return STG_OK;
     if (!d_idx_in || !d_val_in || !d_idx || !d_val) return fail(STG_ERR_INVALID, "null argument");
-    int dev = 0, ncu = 256;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+    int ncu;
+    if (const int rc = device_cus(&ncu)) return rc;
     HIP_TRY(stg::launch_wire_decode(d_idx_in, d_val_in, numel, (uint32_t)flag, d_idx, d_val, ncu,
                                     static_cast<hipStream_t>(stream)));
     return STG_OK;
@@ -2119,33 +1970,21 @@ int stg_wire_decode_batch_device(const stg_wire_rx_t *streams, size_t nstreams, 
         if (w.numel > (size_t)STG_WG * 0xffffffull) return fail(STG_ERR_UNSUPPORTED, "wire stream too long for a batch");
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    stg::WireRxBatch b{};
-    uint64_t blocks = 0;
-    auto flush = [&]() -> int {
-        if (b.nb) HIP_TRY(stg::launch_wire_decode_batch(b, (uint32_t)blocks, s));
-        b = stg::WireRxBatch{};
-        blocks = 0;
-        return STG_OK;
-    };
+    auto b = stream_packer<stg::WireRxBatch>(GRID_MAX, stg::launch_wire_decode_batch, s);
     for (size_t i = 0; i < nstreams; ++i) {
         const stg_wire_rx_t &w = streams[i];
         if (!w.numel) continue;
         const uint64_t nbk = (w.numel + STG_WG - 1) / STG_WG;
-        if (b.nb == stg::WIRE_BATCH || blocks + nbk > 0x7fffffffull) {
-            int rc = flush();
-            if (rc) return rc;
-        }
-        stg::WireRx &d = b.b[b.nb++];
-        d.idx_in = w.d_idx_in;
-        d.val_in = w.d_val_in;
-        d.idx = w.d_idx;
-        d.val = w.d_val;
-        d.n = w.numel;
-        d.flag = (uint32_t)w.flag;
-        d.blk0 = (uint32_t)blocks;
-        blocks += nbk;
+        stg::WireRx *d;
+        if (const int rc = b.add(nbk, &d)) return rc;
+        d->idx_in = w.d_idx_in;
+        d->val_in = w.d_val_in;
+        d->idx = w.d_idx;
+        d->val = w.d_val;
+        d->n = w.numel;
+        d->flag = (uint32_t)w.flag;
     }
-    return flush();
+    return b.flush();
 }
 
 int stg_synth_fill_device(float *d_dst, size_t n, uint64_t seed, int dist, uint32_t param, void *stream) {

@@ -44,6 +44,16 @@ constexpr int QP_XOR2 = 0x4E;  // quad_perm [2,3,0,1]
 
 __device__ __forceinline__ uint32_t lane_id() { return __lane_id(); }
 
+// The item of a batched launch's table this workgroup works on: the host
+// dealt the items consecutive runs of workgroups and wrote each one's first
+// workgroup into its blk0 (batch_pack.h).
+template <class Item>
+__device__ __forceinline__ uint32_t batch_item(const Item *t, uint32_t n) {
+    uint32_t b = 0;
+    while (b + 1 < n && blockIdx.x >= t[b + 1].blk0) ++b;
+    return b;
+}
+
 // Wave-wide inclusive scan of a uint32 (64 lanes) on DPP: row shifts by 1,
 // 2, 4, 8 (lanes shifted in from outside the row of 16 add 0), then the row
 // broadcasts of lanes 15 and 31 into the rows above.  No LDS, no address

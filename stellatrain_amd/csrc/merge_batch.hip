@@ -33,18 +33,12 @@ namespace stg {
 
 namespace {
 
-__device__ __forceinline__ uint32_t tensor_of(const MergeBatchArgs &w) {
-    uint32_t t = 0;
-    while (t + 1 < w.nt && blockIdx.x >= w.t[t + 1].blk0) ++t;
-    return t;
-}
-
 // The election of every tensor of the group: win[j] = 1 + the last position of
 // index j in the tensor's stream; any repeat or index >= n sets the slot's
 // duplicate flag.  One workgroup per MERGE_BATCH_TILE pairs, the emission's
 // partition, so both launches share blk0.
 __global__ void __launch_bounds__(STG_WG) merge_mark_batch(MergeBatchArgs w) {
-    const uint32_t t = tensor_of(w);
+    const uint32_t t = batch_item(w.t, w.nt);
     const MergeTensor &d = w.t[t];
     MergeSlotCtl *c = w.ctl + t;
     const uint32_t tile = blockIdx.x - d.blk0;
@@ -124,7 +118,7 @@ __global__ void __launch_bounds__(STG_WG) merge_emit_batch(MergeBatchArgs w) {
     __shared__ uint64_t s_P, s_psum[STG_WAVES];
     __shared__ uint32_t s_dup;
     const uint32_t tid = threadIdx.x, lane = __lane_id();
-    const uint32_t t = tensor_of(w);
+    const uint32_t t = batch_item(w.t, w.nt);
     const MergeTensor &d = w.t[t];
     MergeSlotCtl *c = w.ctl + t;
     const size_t m = d.m, n = d.n;

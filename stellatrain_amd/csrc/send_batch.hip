@@ -48,9 +48,7 @@ __device__ __forceinline__ void gather_one(const SendGather &a, size_t e) {
 // tile is scalar.  Every element is read and written by exactly one lane.
 template <uint32_t MAXS>
 __global__ void __launch_bounds__(STG_WG) gather_add_batch(SendGatherBatch w) {
-    uint32_t b = 0;
-    while (b + 1 < w.nt && blockIdx.x >= w.t[b + 1].blk0) ++b;
-    const SendGather &a = w.t[b];
+    const SendGather &a = w.t[batch_item(w.t, w.nt)];
     const size_t wb = blockIdx.x - a.blk0;
     if (!a.vec) {
         for (uint32_t u = 0; u < SEND_GATHER_TILE / STG_WG; ++u) {
@@ -104,9 +102,7 @@ __global__ void __launch_bounds__(STG_WG) gather_add_batch(SendGatherBatch w) {
 // idx_cap > count (d.zero0) element 0 is zeroed too, by the first workgroup
 // after the barrier (element 0 is a tail element when n < 16).
 __global__ void __launch_bounds__(STG_WG) ef_pack_batch(SendFinishBatch w) {
-    uint32_t b = 0;
-    while (b + 1 < w.nt && blockIdx.x >= w.t[b + 1].blk0) ++b;
-    const SendFinish &d = w.t[b];
+    const SendFinish &d = w.t[batch_item(w.t, w.nt)];
     const uint32_t wb = blockIdx.x - d.blk0;
     const size_t full = d.n / 16 * 16;
     const bool ef = d.resid != nullptr;

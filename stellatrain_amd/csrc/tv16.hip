@@ -712,37 +712,54 @@ uint32_t crew_lone(uint32_t num_cu, uint32_t others) {
     return std::min(std::max(room, MAX_BATCH + 1u), 1024u);
 }
 
-}  // namespace
+// The launcher's runtime switches, each read once.
+struct Switches {
+    int stage;           // STG_DEBUG_TV16_STAGE (1 / 3: the batched scan built to stop there, no fill)
+    bool lfin;           // STG_TV16_LFIN=0: no one-bucket path (the batched scan takes one bucket too)
+    bool lf2;            // STG_TV16_LF2=0: the one-bucket scan launch does not finish the call itself
+    bool count;          // STG_DEBUG_TV16_COUNT: the scan counts its launches and dead workgroups
+    uint32_t fill_mode;  // STG_DEBUG_TV16_FILL (Tv16FillArgs::mode, LScanArgs::mode)
+    uint32_t skip;       // STG_LF2_SKIP (LScanArgs::skip)
+    uint32_t rankers;    // STG_TV16_LFIN_RANKERS (0 .. 128; 8)
+};
+const Switches &switches() {
+    static const Switches v = [] {
+        const auto num = [](const char *e, int dflt) { return e ? atoi(e) : dflt; };
+        Switches w;
+        w.stage = num(getenv("STG_DEBUG_TV16_STAGE"), 0);
+        w.lfin = num(getenv("STG_TV16_LFIN"), 1) != 0;
+        w.lf2 = num(getenv("STG_TV16_LF2"), 1) != 0;
+        w.count = num(getenv("STG_DEBUG_TV16_COUNT"), 0) != 0;
+        w.fill_mode = (uint32_t)num(getenv("STG_DEBUG_TV16_FILL"), 0);
+        w.skip = (uint32_t)num(getenv("STG_LF2_SKIP"), 0);
+        w.rankers = (uint32_t)std::max(0, std::min(num(getenv("STG_TV16_LFIN_RANKERS"), 8), 128));
+        return w;
+    }();
+    return v;
+}
 
-hipError_t launch_tv16(const Tv16Launch &a, const DevWS &ws, hipStream_t s) {
-    if (!a.nb) return hipSuccess;
-    if (a.nb > MAX_BATCH || !a.epoch || a.epoch >= (1u << 24)) return hipErrorInvalidValue;
-    BatchArgs A{};
-    Tv16FillArgs F{};
-    uint32_t K = 0;
-    static const int dbg_stage = getenv("STG_DEBUG_TV16_STAGE") ? atoi(getenv("STG_DEBUG_TV16_STAGE")) : 0;
-    constexpr bool lone_ok = true;
-    // the one-bucket path: a scan with no waits between workgroups, finished
-    // by the fill launch (tv16lone.hip; STG_TV16_LFIN=0: the batched scan)
-    static const bool lfin_ok = !(getenv("STG_TV16_LFIN") && atoi(getenv("STG_TV16_LFIN")) == 0);
-    auto lone_chunks = [](size_t n) { return std::max<uint32_t>(1, (uint32_t)((n / 16 + LCHUNK - 1) / LCHUNK)); };
-    const bool lone_path = lone_ok && lfin_ok && a.nb == 1 && !dbg_stage && lone_chunks(a.b[0].n) <= a.lone_cap &&
-                           lone_chunks(a.b[0].n) <= LMAXC && ws.ldesc;
-    // a gather-add rides in the one-bucket scan (not on a key's first call,
-    // whose threshold is taken from the bucket before the scan); elsewhere it
-    // runs as its own pass first
-    bool fused_gather = false;
+uint32_t lone_chunks(size_t n) { return std::max<uint32_t>(1, (uint32_t)((n / 16 + LCHUNK - 1) / LCHUNK)); }
+
+// The launch's buckets made ready: a gather-add rides in the one-bucket scan
+// (*fused_gather; not on a key's first call, whose threshold is taken from the
+// bucket before the scan) and elsewhere runs as its own pass first; a key's
+// first threshold; then the scan's and the fill's tables, and the fields the
+// fill launch has on either path.
+hipError_t prepare_buckets(const Tv16Launch &a, const DevWS &ws, bool lone_path, BatchArgs &A, Tv16FillArgs &F,
+                           bool *fused_gather, hipStream_t s) {
+    *fused_gather = false;
     for (uint32_t i = 0; i < a.nb; ++i) {
         const Tv16Bucket &b = a.b[i];
         if (!b.gather || (!b.gather->resid && b.gather->nsrc <= 1)) continue;  // (no term to add)
         if (b.gather->dst != b.src) return hipErrorInvalidValue;
         if (lone_path && !b.first) {
-            fused_gather = true;
+            *fused_gather = true;
         } else {
             const hipError_t e = launch_gather_add(*b.gather, 0, b.n, a.num_cu, s);
             if (e != hipSuccess) return e;
         }
     }
+    uint32_t K = 0;
     for (uint32_t i = 0; i < a.nb; ++i) {
         const Tv16Bucket &b = a.b[i];
         if (b.first) {  // first threshold from sequential line sums (thresholdv16.cpp:36-54)
@@ -788,8 +805,6 @@ hipError_t launch_tv16(const Tv16Launch &a, const DevWS &ws, hipStream_t s) {
         f.heap = reinterpret_cast<uint2 *>(b.sums);
     }
     if (K > a.desc_cap) return hipErrorInvalidValue;
-    bool ef = false;  // any bucket with a residual: the fused error-feedback instantiation
-    for (uint32_t i = 0; i < a.nb; ++i) ef |= a.b[i].resid != nullptr;
     A.nbk = a.nb;
     A.epoch = a.epoch;
     A.K = K;
@@ -797,115 +812,115 @@ hipError_t launch_tv16(const Tv16Launch &a, const DevWS &ws, hipStream_t s) {
     A.desc = ws.desc;
     A.cand = ws.cand;
     A.fail = ws.fail;
+    A.dbg = switches().count ? ws.misc : nullptr;
+    F.nbk = a.nb;
+    F.epoch = a.epoch;
+    F.dec = ws.ctl->dec;
+    F.fail = ws.fail;
+    F.dbg = ws.misc;
+    F.mode = switches().fill_mode;
+    F.cc = &ws.ctl->cc[a.epoch & 1u];
+    F.crew_ctl = ws.crew;
+    return hipSuccess;
+}
+
+// The one-bucket path: a scan with no waits between workgroups (tv16lone.hip),
+// finished inside its own launch (tv16lf2.h) or by the fill launch.
+hipError_t launch_lone(const Tv16Launch &a, const DevWS &ws, const BatchArgs &A, Tv16FillArgs &F, bool fused_gather,
+                       hipStream_t s) {
+    const Tv16Bucket &b = a.b[0];
+    const uint32_t KL = lone_chunks(b.n);  // one-bucket chunks
+    if (a.ev) (void)hipEventRecord(a.ev[0], s);
+    LScanArgs L{};
+    L.src = b.src;
+    L.nb = A.bk[0].nb;
+    L.nc = KL;
+    L.state = b.state;
+    L.cp = ws.cp;
+    L.resid = b.resid;
+    L.ldesc = ws.ldesc;
+    L.lq = ws.lq;
+    L.lw = ws.lw;
+    L.lv = ws.lv;
+    L.went = ws.went;
+    L.zero_next = reinterpret_cast<uint32_t *>(&ws.ctl->cc[(a.epoch + 1) & 1u]);
+    // the window histogram and the finish's arrival block by call parity:
+    // this call's copies were zeroed by the previous call's scan
+    uint32_t tag = a.epoch;
+    if (a.lone_calls) {
+        if (++*a.lone_calls == 0) *a.lone_calls = 2;  // (0 is never a tag; the parity keeps alternating)
+        tag = *a.lone_calls;
+    }
+    const uint32_t par = tag & 1u;
+    L.whist = ws.whist + (size_t)par * LNBIN;
+    L.whist_next = ws.whist + (size_t)(par ^ 1u) * LNBIN;
+    L.tag = tag;
+    L.done = ws.larr;
+    L.tl = (uint32_t)(b.n % 16);
+    // the finish inside the scan launch (tv16lf2.h), not for the wire form:
+    // 48 workers + 16 rankers (profiles/r05_lf2_roles_sweep.txt)
+    constexpr uint32_t lf2_fin = 64, lf2_wk = 48;
+    static_assert(lf2_wk < lf2_fin && lf2_fin <= LF2_MAXF, "roles");
+    L.fin = switches().lf2 && !b.wflag ? lf2_fin : 0u;
+    L.nwk = lf2_wk;
+    L.mode = switches().fill_mode;
+    L.out_idx = b.idx;
+    L.out_val = b.val;
+    L.count_out = b.count_out;
+    L.dst_len = b.dst_len;
+    L.idx_offset = b.idx_offset;
+    L.fail = ws.fail;
+    L.dbg = ws.misc;
+    L.skip = switches().skip;
+    if (fused_gather) {  // (bucket 0's gather has a term to add)
+        const GatherArgs &g = *b.gather;
+        L.gres = g.resid;
+        for (uint32_t x = 1; x < g.nsrc && x < GATHER_MAX; ++x) L.gsrc[x] = g.src[x];
+        L.gn = std::max<uint32_t>(1, g.nsrc);
+    }
+    hipError_t e = launch_tv16_lscan(L, a.num_cu, s);  // (clamps L.fin to what the grid allows)
+    if (e != hipSuccess) return e;
+    if (a.ev) (void)hipEventRecord(a.ev[1], s);
+    constexpr uint32_t workers = 64;
+    F.lone = true;
+    F.helpers = 0;
+    F.lfin = true;
+    F.workers = workers;
+    F.rankers = switches().rankers;
+    F.nc = KL;
+    F.ldesc = ws.ldesc;
+    F.lq = ws.lq;
+    F.lw = ws.lw;
+    F.lv = ws.lv;
+    F.whist = L.whist;
+    F.went = ws.went;
+    F.state = b.state;
+    F.cp = ws.cp;
+    F.resid = b.resid;
+    F.fin = L.fin;
+    F.fin_tag = L.tag;
+    F.fin_done = L.done;
+    F.crew = crew_lone(a.num_cu, workers + F.rankers);
+    if ((e = launch_tv16_fill_any(F, s)) != hipSuccess) return e;
+    if (a.ev) (void)hipEventRecord(a.ev[2], s);
+    return hipGetLastError();
+}
+
+// The batched scan, then the regime-B heap fill: one workgroup per bucket,
+// stream-ordered after the scan.
+hipError_t launch_batched(const Tv16Launch &a, const BatchArgs &A, Tv16FillArgs &F, hipStream_t s) {
     // this launch's share of the device's two scan workgroups per CU, sized
     // by the caller (scan_grid.h: all of them for one stream, launches from
     // several streams split them with some oversubscription; no more than the
     // chunks need).  Chunks are taken dynamically: any G >= 1 gives the same
     // result, and co-residency is not required.
     const uint32_t G = std::max<uint32_t>(1, std::min<uint32_t>(a.max_wg, TV16_MAXG));
-    static const bool dbg_count = getenv("STG_DEBUG_TV16_COUNT") && atoi(getenv("STG_DEBUG_TV16_COUNT")) != 0;
-    A.dbg = dbg_count ? ws.misc : nullptr;
-    const bool lone_scan = lone_ok && a.nb == 1;
-    const uint32_t KL = lone_chunks(a.b[0].n);  // one-bucket chunks
-    if (lone_path) {
-        if (a.ev) (void)hipEventRecord(a.ev[0], s);
-        LScanArgs L{};
-        L.src = a.b[0].src;
-        L.nb = A.bk[0].nb;
-        L.nc = KL;
-        L.state = a.b[0].state;
-        L.cp = ws.cp;
-        L.resid = a.b[0].resid;
-        L.ldesc = ws.ldesc;
-        L.lq = ws.lq;
-        L.lw = ws.lw;
-        L.lv = ws.lv;
-        L.whist = ws.whist;
-        L.went = ws.went;
-        L.zero_next = reinterpret_cast<uint32_t *>(&ws.ctl->cc[(a.epoch + 1) & 1u]);
-        // the window histogram and the finish's arrival block by call parity:
-        // this call's copies were zeroed by the previous call's scan
-        uint32_t tag = a.epoch;
-        if (a.lone_calls) {
-            if (++*a.lone_calls == 0) *a.lone_calls = 2;  // (0 is never a tag; the parity keeps alternating)
-            tag = *a.lone_calls;
-        }
-        const uint32_t par = tag & 1u;
-        L.whist = ws.whist + (size_t)par * LNBIN;
-        L.whist_next = ws.whist + (size_t)(par ^ 1u) * LNBIN;
-        L.tag = tag;
-        L.done = ws.larr;
-        L.tl = (uint32_t)(a.b[0].n % 16);
-        // the finish inside the scan launch (tv16lf2.h): not for the wire form
-        static const int lf2_env = getenv("STG_TV16_LF2") ? atoi(getenv("STG_TV16_LF2")) : 1;
-        // 48 workers + 16 rankers (profiles/r05_lf2_roles_sweep.txt)
-        constexpr uint32_t lf2_fin = 64, lf2_wk = 48;
-        static_assert(lf2_fin <= LF2_MAXF, "roles");
-        {
-            static const uint32_t fill_mode0 =
-                getenv("STG_DEBUG_TV16_FILL") ? (uint32_t)atoi(getenv("STG_DEBUG_TV16_FILL")) : 0u;
-            const bool lf2 = lf2_env != 0 && !a.b[0].wflag && lf2_fin > lf2_wk;
-            L.fin = lf2 ? lf2_fin : 0u;
-            L.nwk = lf2_wk;
-            L.mode = fill_mode0;
-            L.out_idx = a.b[0].idx;
-            L.out_val = a.b[0].val;
-            L.count_out = a.b[0].count_out;
-            L.dst_len = a.b[0].dst_len;
-            L.idx_offset = a.b[0].idx_offset;
-            L.fail = ws.fail;
-            L.dbg = ws.misc;
-            static const uint32_t skip = getenv("STG_LF2_SKIP") ? (uint32_t)atoi(getenv("STG_LF2_SKIP")) : 0u;
-            L.skip = skip;
-        }
-        if (fused_gather) {  // (fused_gather: bucket 0's gather has a term to add)
-            const GatherArgs &g = *a.b[0].gather;
-            L.gres = g.resid;
-            for (uint32_t x = 1; x < g.nsrc && x < GATHER_MAX; ++x) L.gsrc[x] = g.src[x];
-            L.gn = std::max<uint32_t>(1, g.nsrc);
-            L.tl = (uint32_t)(a.b[0].n % 16);
-        }
-        hipError_t e = launch_tv16_lscan(L, a.num_cu, s);  // (clamps L.fin to what the grid allows)
-        if (e != hipSuccess) return e;
-        if (a.ev) (void)hipEventRecord(a.ev[1], s);
-        F.nbk = 1;
-        F.epoch = a.epoch;
-        F.dec = ws.ctl->dec;
-        F.fail = ws.fail;
-        F.dbg = ws.misc;
-        static const uint32_t fill_mode =
-            getenv("STG_DEBUG_TV16_FILL") ? (uint32_t)atoi(getenv("STG_DEBUG_TV16_FILL")) : 0u;
-        F.mode = fill_mode;
-        F.lone = true;
-        constexpr uint32_t workers = 64;
-        static const uint32_t rankers = std::max(0, std::min(
-            getenv("STG_TV16_LFIN_RANKERS") ? atoi(getenv("STG_TV16_LFIN_RANKERS")) : 8, 128));
-        F.helpers = 0;
-        F.cc = &ws.ctl->cc[a.epoch & 1u];
-        F.lfin = true;
-        F.workers = workers;
-        F.rankers = rankers;
-        F.nc = KL;
-        F.ldesc = ws.ldesc;
-        F.lq = ws.lq;
-        F.lw = ws.lw;
-        F.lv = ws.lv;
-        F.whist = L.whist;
-        F.went = ws.went;
-        F.state = a.b[0].state;
-        F.cp = ws.cp;
-        F.resid = a.b[0].resid;
-        F.fin = L.fin;
-        F.fin_tag = L.tag;
-        F.fin_done = L.done;
-        F.crew = crew_lone(a.num_cu, workers + rankers);
-        F.crew_ctl = ws.crew;
-        if ((e = launch_tv16_fill_any(F, s)) != hipSuccess) return e;
-        if (a.ev) (void)hipEventRecord(a.ev[2], s);
-        return hipGetLastError();
-    }
+    const int stage = switches().stage;
+    const bool lone_scan = a.nb == 1;
+    bool ef = false;  // any bucket with a residual: the fused error-feedback instantiation
+    for (uint32_t i = 0; i < a.nb; ++i) ef |= a.b[i].resid != nullptr;
     if (a.ev) (void)hipEventRecord(a.ev[0], s);
-    switch (dbg_stage) {
+    switch (stage) {
         case 1: tv16_batch<1, false, false><<<G, FWG, 0, s>>>(A); break;
         case 3: tv16_batch<3, false, false><<<G, FWG, 0, s>>>(A); break;
         default:
@@ -915,26 +930,33 @@ hipError_t launch_tv16(const Tv16Launch &a, const DevWS &ws, hipStream_t s) {
             break;
     }
     if (a.ev) (void)hipEventRecord(a.ev[1], s);
-    if (dbg_stage != 1 && dbg_stage != 3) {
-        // regime-B heap fill: one workgroup per bucket, stream-ordered after the scan
-        F.nbk = a.nb;
-        F.epoch = a.epoch;
-        F.dec = ws.ctl->dec;
-        F.fail = ws.fail;
-        F.dbg = ws.misc;
-        static const uint32_t fill_mode =
-            getenv("STG_DEBUG_TV16_FILL") ? (uint32_t)atoi(getenv("STG_DEBUG_TV16_FILL")) : 0u;
-        F.mode = fill_mode;
+    if (stage != 1 && stage != 3) {
         F.lone = lone_scan;
         F.helpers = F.lone ? 15u : 0u;
-        F.cc = &ws.ctl->cc[a.epoch & 1u];
         F.crew = F.lone ? crew_lone(a.num_cu, F.nbk + F.helpers) : crew_batch();
-        F.crew_ctl = ws.crew;
         const hipError_t e = launch_tv16_fill_any(F, s);
         if (e != hipSuccess) return e;
     }
     if (a.ev) (void)hipEventRecord(a.ev[2], s);
     return hipGetLastError();
+}
+
+}  // namespace
+
+bool tv16_debug_count() { return switches().count; }
+
+hipError_t launch_tv16(const Tv16Launch &a, const DevWS &ws, hipStream_t s) {
+    if (!a.nb) return hipSuccess;
+    if (a.nb > MAX_BATCH || !a.epoch || a.epoch >= (1u << 24)) return hipErrorInvalidValue;
+    // the one-bucket path, where its lists hold the bucket's chunks
+    const bool lone_path = switches().lfin && a.nb == 1 && !switches().stage && lone_chunks(a.b[0].n) <= a.lone_cap &&
+                           lone_chunks(a.b[0].n) <= LMAXC && ws.ldesc;
+    BatchArgs A{};
+    Tv16FillArgs F{};
+    bool fused_gather = false;
+    const hipError_t e = prepare_buckets(a, ws, lone_path, A, F, &fused_gather, s);
+    if (e != hipSuccess) return e;
+    return lone_path ? launch_lone(a, ws, A, F, fused_gather, s) : launch_batched(a, A, F, s);
 }
 
 }  // namespace stg

@@ -43,9 +43,7 @@ __device__ __forceinline__ void encode_one(const uint32_t *__restrict__ idx, con
 // Batched encode: the launch's workgroups are dealt to the buckets by the
 // host-computed first-workgroup offsets (blk0), one element per lane.
 __global__ void __launch_bounds__(STG_WG) wire_encode_batch(WireBatch w) {
-    uint32_t b = 0;
-    while (b + 1 < w.nb && blockIdx.x >= w.b[b + 1].blk0) ++b;
-    const WireBucket &d = w.b[b];
+    const WireBucket &d = w.t[batch_item(w.t, w.nt)];
     const size_t i = (size_t)(blockIdx.x - d.blk0) * STG_WG + threadIdx.x;
     if (i < d.n) encode_one(d.idx, d.val, i, d.n ? 8 * ((d.n - 1) / 8) : 0, d.flag, d.idx_out, d.val_out);
 }
@@ -71,9 +69,7 @@ __global__ void __launch_bounds__(STG_WG) wire_decode(const void *__restrict__ i
 
 // Batched decode: workgroups dealt to the streams as in wire_encode_batch.
 __global__ void __launch_bounds__(STG_WG) wire_decode_batch(WireRxBatch w) {
-    uint32_t b = 0;
-    while (b + 1 < w.nb && blockIdx.x >= w.b[b + 1].blk0) ++b;
-    const WireRx &d = w.b[b];
+    const WireRx &d = w.t[batch_item(w.t, w.nt)];
     const size_t i = (size_t)(blockIdx.x - d.blk0) * STG_WG + threadIdx.x;
     if (i < d.n) {
         const size_t wend = 8 * ((d.n - 1) / 8);
@@ -103,13 +99,13 @@ hipError_t launch_wire_decode(const void *idx_in, const void *val_in, size_t n, 
 }
 
 hipError_t launch_wire_decode_batch(const WireRxBatch &w, uint32_t blocks, hipStream_t s) {
-    if (!w.nb || !blocks) return hipSuccess;
+    if (!w.nt || !blocks) return hipSuccess;
     wire_decode_batch<<<blocks, STG_WG, 0, s>>>(w);
     return hipGetLastError();
 }
 
 hipError_t launch_wire_encode_batch(const WireBatch &w, uint32_t blocks, hipStream_t s) {
-    if (!w.nb || !blocks) return hipSuccess;
+    if (!w.nt || !blocks) return hipSuccess;
     wire_encode_batch<<<blocks, STG_WG, 0, s>>>(w);
     return hipGetLastError();
 }

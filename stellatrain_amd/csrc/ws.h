@@ -206,6 +206,7 @@ struct Tv16Launch {
                            // window histogram and arrival block, each call zeroing the other copy)
 };
 hipError_t launch_tv16(const Tv16Launch &a, const DevWS &ws, hipStream_t s);
+bool tv16_debug_count();  // STG_DEBUG_TV16_COUNT, as the launcher read it (tv16.hip)
 // thresholdv16 regime-B heap fill (tv16fill.hip): one workgroup per bucket
 struct Tv16FillBucket {
     const float *src;
@@ -483,8 +484,8 @@ struct WireBucket {
     uint32_t flag, blk0;  // blk0: first workgroup of this bucket in the launch
 };
 struct WireBatch {
-    WireBucket b[WIRE_BATCH];
-    uint32_t nb;
+    WireBucket t[WIRE_BATCH];
+    uint32_t nt;
 };
 hipError_t launch_wire_encode_batch(const WireBatch &w, uint32_t blocks, hipStream_t s);
 // The one-call MERGE send path (send_batch.hip): the gather-add before the
@@ -533,8 +534,8 @@ struct WireRx {  // one received stream of a batched decode
     uint32_t flag, blk0;  // blk0: first workgroup of this stream in the launch
 };
 struct WireRxBatch {
-    WireRx b[WIRE_BATCH];
-    uint32_t nb;
+    WireRx t[WIRE_BATCH];
+    uint32_t nt;
 };
 hipError_t launch_wire_decode_batch(const WireRxBatch &w, uint32_t blocks, hipStream_t s);
 hipError_t launch_wire_encode(const uint32_t *idx, const float *val, size_t n, uint32_t flag, void *idx_out,
