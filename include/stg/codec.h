@@ -249,7 +249,10 @@ int stg_codec_check(stg_codec_t h);
  * stg_merge_optimize_{sgd,adam}_batch_device calls use the same scratch: a
  * launch of theirs takes 4 B per element of the sum of its tensors' n, a sum
  * capped at 8 Mi (32 MiB; one larger tensor: its own n), 8 B per 1,024-pair
- * tile of its tensors, and 6 KiB of per-slot hand-off words. */
+ * tile of its tensors, and 6 KiB of per-slot hand-off words; a world > 1
+ * group of theirs takes 13 B per element of the sum of its tensors' n (each n
+ * rounded up to 16), a sum capped at 4 Mi: 32 MiB of winner words, 16 MiB of
+ * dense floats, 4 MiB of mark bytes, and 8 B per 4,096-element tile. */
 int stg_scatter_merge_device(const uint32_t *d_idx, const float *d_val, size_t per_rank, int world, size_t n,
                              float *d_dense, uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
                              uint32_t *d_out_count, void *stream);
@@ -482,9 +485,23 @@ typedef struct stg_merge_task {
  * in order as they would one by one.  Tensors of different names must not
  * overlap in memory (parameters, streams or outputs): tasks of one launch run
  * concurrently.
- *   Not batched: a task with world > 1 or per_rank == 0, and every task of an
- * Adam handle with amsgrad, runs the per-tensor sequence at its place in the
- * order.
+ *   Batched as well: tasks with world > 1, per_rank > 0 and such an optimizer.
+ * Up to 16 consecutive tasks of the same world form a group that shares
+ * world + 4 launches: world + 1 that scatter rank r - 1 and elect rank r of
+ * every tensor (one launch per rank, so each element's sum keeps the rank
+ * order), the mark count, its scan, and the emission with the step on every
+ * emitted pair.  A group also closes on a change of world (or to world 1),
+ * before a task whose name already occurs in it, and before the sum of its
+ * tensors' param_len would pass 4 Mi.  It works on slices of the (device,
+ * stream) scratch -- per tensor 2 n winner words, n dense floats and n mark
+ * bytes, each slice 16-byte aligned, zero between calls (sizes: see
+ * stg_scatter_merge_device) -- and not on the tasks' d_dense / d_mark, which
+ * are still required and checked and stay zero; one dense / mark pair may
+ * serve every task of the call.  A tensor of more than 4 Mi elements runs the
+ * per-tensor sequence on the caller's scratch.
+ *   Not batched: a task with per_rank == 0, a world > 1 task above that size,
+ * and every task of an Adam handle with amsgrad, runs the per-tensor sequence
+ * at its place in the order.
  *   All or nothing: every task is checked before any device call or state
  * change -- a null handle or name, a null `tasks` with ntasks > 0, the
  * conditions of stg_scatter_merge_wire_device, an empty parameter or 2^32
@@ -500,6 +517,14 @@ typedef struct stg_merge_task {
  * (stg_scatter_merge_check). */
 int stg_merge_optimize_sgd_batch_device(stg_sgd_t o, const stg_merge_task_t *tasks, size_t ntasks, void *stream);
 int stg_merge_optimize_adam_batch_device(stg_adam_t o, const stg_merge_task_t *tasks, size_t ntasks, void *stream);
+/* *out: the kernel launches the two batched calls above have enqueued on
+ * (current device, stream) since its scratch was created -- the shared launches
+ * and the per-tensor sequences run at their place, their step launches
+ * included -- counted as each launch is enqueued.  The results of a batched call
+ * are those of the loop, so this is how a caller sees what was shared.  0 when
+ * the stream has no scratch (yet, or after stg_scatter_merge_release).
+ * STG_ERR_INVALID for a null `out`, before any device call. */
+int stg_merge_batch_launches(void *stream, uint64_t *out);
 
 /* Synthetic fp32 buckets from the integer-only generator of SURVEY 8(d)
  * (dist 0 = D1, 1 = D2 heavy tail, 2 = D3 zeros with prob param/1e4);

@@ -141,23 +141,7 @@ __global__ void __launch_bounds__(STG_WG) scatter_mark_w(const void *__restrict_
     }
 }
 
-__device__ __forceinline__ uint32_t nz_bytes(uint32_t w) {
-    uint32_t c = 0;
-    c += (w & 0xffu) != 0;
-    c += (w & 0xff00u) != 0;
-    c += (w & 0xff0000u) != 0;
-    c += (w & 0xff000000u) != 0;
-    return c;
-}
-
-__device__ __forceinline__ uint4 load_marks(const uint8_t *mark, size_t n, size_t e) {
-    if (e + 16 <= n) return *reinterpret_cast<const uint4 *>(mark + e);
-    uint32_t w[4] = {0, 0, 0, 0};
-    for (uint32_t b = 0; b < 16; ++b)
-        if (e + b < n) w[b >> 2] |= (uint32_t)mark[e + b] << (8 * (b & 3));
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
+// (nz_bytes and load_marks: merge_dev.h, shared with merge_batch_world.hip)
 __global__ void __launch_bounds__(STG_WG) mark_count(const uint8_t *__restrict__ mark, size_t n,
                                                      uint32_t *__restrict__ tile_cnt) {
     __shared__ uint32_t s[STG_WAVES];
@@ -708,7 +692,8 @@ hipError_t launch_error_feedback(float *grad, size_t n, const uint32_t *idx, siz
 
 // world > 1, after the ranks' scatters: the marked indices in order.
 static hipError_t launch_mark_emit(size_t n, int world, float *dense, uint8_t *mark, uint32_t *out_idx,
-                                   float *out_val, uint32_t *out_count, uint32_t *scratch_tiles, hipStream_t s) {
+                                   float *out_val, uint32_t *out_count, uint32_t *scratch_tiles, hipStream_t s,
+                                   uint64_t *launches) {
     const uint32_t ntiles = (uint32_t)((n + MARK_TILE - 1) / MARK_TILE);
     if (!ntiles) return hipMemsetAsync(out_count, 0, sizeof(uint32_t), s);
     // per-tile counts, their scan, then one workgroup per tile (the old
@@ -716,6 +701,7 @@ static hipError_t launch_mark_emit(size_t n, int world, float *dense, uint8_t *m
     mark_count<<<ntiles, STG_WG, 0, s>>>(mark, n, scratch_tiles);
     mark_scan<<<1, 1024, 0, s>>>(scratch_tiles, ntiles, out_count);
     mark_emit_tile<<<ntiles, STG_WG, 0, s>>>(mark, dense, n, ntiles, (float)world, scratch_tiles, out_idx, out_val);
+    count_launch(launches, 3);
     return hipGetLastError();
 }
 
@@ -728,7 +714,7 @@ static const float *val32(const RankStream *k) { return k ? static_cast<const fl
 hipError_t launch_scatter_merge(const RankStream *ranks, size_t per_rank, int world, size_t n, float *dense,
                                 uint8_t *mark, uint32_t *out_idx, float *out_val, uint32_t *out_count,
                                 uint32_t *scratch_tiles, uint32_t *win, int num_cu, hipStream_t s,
-                                const Win1Desc &w1) {
+                                const Win1Desc &w1, uint64_t *launches) {
     const size_t wend = per_rank ? 8 * ((per_rank - 1) / 8) : 0;
     if (world == 1) {
         if (!per_rank) return hipMemsetAsync(out_count, 0, sizeof(uint32_t), s);
@@ -753,6 +739,7 @@ hipError_t launch_scatter_merge(const RankStream *ranks, size_t per_rank, int wo
             if (smart) win_emit1t<wp, true><<<nt1, STG_WG, 0, s>>>(a);
             else win_emit1t<wp, false><<<nt1, STG_WG, 0, s>>>(a);
         }
+        count_launch(launches, 2);  // the election and the emission
         return hipGetLastError();
     }
     // rank r's scatter beside rank r+1's election (parity halves of `win`,
@@ -770,19 +757,22 @@ hipError_t launch_scatter_merge(const RankStream *ranks, size_t per_rank, int wo
                 scatter_mark_w<<<b2, STG_WG, 0, s>>>(sc ? sc->idx : nullptr, sc ? sc->val : nullptr,
                                                      sc ? sc->flag : 0u, swin, mk ? mk->idx : nullptr,
                                                      mk ? mk->flag : 0u, mwin, per_rank, n, wend, dense, mark);
+            count_launch(launches);
         }
     }
-    return launch_mark_emit(n, world, dense, mark, out_idx, out_val, out_count, scratch_tiles, s);
+    return launch_mark_emit(n, world, dense, mark, out_idx, out_val, out_count, scratch_tiles, s, launches);
 }
 
-hipError_t launch_sgd(const SgdLaunch &a, hipStream_t s) {
+hipError_t launch_sgd(const SgdLaunch &a, hipStream_t s, uint64_t *launches) {
     const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((a.grad_len + STG_WG - 1) / STG_WG, 2048));
     if (a.last) sgd_apply<true><<<blocks, STG_WG, 0, s>>>(a);
     else sgd_apply<false><<<blocks, STG_WG, 0, s>>>(a);
+    count_launch(launches);
     return hipGetLastError();
 }
 
-hipError_t launch_adam(const AdamLaunch &a, hipStream_t s) {
+hipError_t launch_adam(const AdamLaunch &a, hipStream_t s, uint64_t *launches) {
+    count_launch(launches);  // one launch on either path
     if (!a.amsgrad) {
         const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((a.grad_len + STG_WG - 1) / STG_WG, 2048));
         adam_apply<<<blocks, STG_WG, 0, s>>>(a);

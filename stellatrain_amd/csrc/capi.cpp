@@ -639,6 +639,13 @@ struct MergeScratch {
     // batched launches (merge_batch.hip): a ticket, duplicate flag and failed-launch
     // tag per tensor slot, zero at creation; they share win, desc, tag and fail
     stg::DevBuf<stg::MergeSlotCtl> bctl;
+    // batched world > 1 groups (merge_batch_world.hip): the group's dense floats
+    // and mark bytes, zero at creation and after every call; its winner words
+    // are `win`, its tile counts `tiles`
+    stg::DevBuf<float> wdense;
+    stg::DevBuf<uint8_t> wmark;
+    // kernel launches the batched entries have enqueued on this stream (stg_merge_batch_launches)
+    uint64_t launches = 0;
     ~MergeScratch() { (void)hipSetDevice(device); }  // (the members free on this device)
 };
 std::mutex g_merge_mu;
@@ -655,7 +662,10 @@ std::shared_ptr<MergeScratch> merge_scratch(int dev, hipStream_t s) {
 
 // Caller holds m->mu.  min_tiles: tagged tile counts a batched launch needs
 // (the sum of its tensors' tiles; n is then the sum of their lengths).
-int merge_scratch_ensure(MergeScratch *m, hipStream_t s, size_t n, size_t per_rank, int world, size_t min_tiles = 0) {
+// group: elements of dense and marks a batched world > 1 group needs (n is then
+// that too, and world > 1: two winner words per element).
+int merge_scratch_ensure(MergeScratch *m, hipStream_t s, size_t n, size_t per_rank, int world, size_t min_tiles = 0,
+                         size_t group = 0) {
     // per-tile counts and their prefixes (the world > 1 mark scan)
     // ... and the world-1 emission's tagged tile counts (tiles of >= MERGE_TILE / 16 pairs)
     const size_t tiles = std::max({2 * ((std::max(n, per_rank) + stg::MERGE_TILE - 1) / stg::MERGE_TILE) + 2,
@@ -668,6 +678,10 @@ int merge_scratch_ensure(MergeScratch *m, hipStream_t s, size_t n, size_t per_ra
     // [0] sticky failure bits, [1] the tag of the last call that failed
     HIP_TRY(m->fail.reserve(2, s, true));
     if (min_tiles) HIP_TRY(m->bctl.reserve(stg::MERGE_BATCH, s, true));
+    if (group) {
+        HIP_TRY(m->wdense.reserve(group, s, true));
+        HIP_TRY(m->wmark.reserve(group, s, true));
+    }
     const size_t words = std::max<size_t>(world > 1 ? 2 * n : n, 1);  // world > 1: two election halves
     HIP_TRY(m->win.reserve(words, s, true));
     return STG_OK;
@@ -1244,7 +1258,7 @@ static int merge_size_check(const MergeCall &c) {
 // merge_run on a scratch the caller has looked up and locked (ms->mu held; the
 // scratch of the current device and c.stream): size it, tag the call, launch.
 static int merge_run_locked(const MergeCall &c, MergeScratch *ms, int ncu, const stg::SgdLaunch *sgd,
-                            const stg::AdamLaunch *adam) {
+                            const stg::AdamLaunch *adam, uint64_t *launches = nullptr) {
     hipStream_t s = static_cast<hipStream_t>(c.stream);
     int rc = merge_scratch_ensure(ms, s, c.n, c.per_rank, c.world);
     if (rc) return rc;
@@ -1252,7 +1266,7 @@ static int merge_run_locked(const MergeCall &c, MergeScratch *ms, int ncu, const
     const stg::Win1Desc w1{ms->desc.get(), ms->ticket.get(), ms->tag, ms->fail.get(),
                            reinterpret_cast<uint32_t *>(ms->ticket.get() + 1), sgd, adam};
     HIP_TRY(stg::launch_scatter_merge(c.rs.data(), c.per_rank, c.world, c.n, c.dense, c.mark, c.out_idx, c.out_val,
-                                      c.out_count, ms->tiles.get(), ms->win.get(), ncu, s, w1));
+                                      c.out_count, ms->tiles.get(), ms->win.get(), ncu, s, w1, launches));
     return STG_OK;
 }
 
@@ -1370,12 +1384,14 @@ struct SgdBatch {
         *out = a;
         return STG_OK;
     }
-    static hipError_t launch(const Launch &a, hipStream_t s) { return stg::launch_sgd(a, s); }
+    static hipError_t launch(const Launch &a, hipStream_t s, uint64_t *n) { return stg::launch_sgd(a, s, n); }
     static const stg::SgdLaunch *sgd(const Launch *a) { return a; }
     static const stg::AdamLaunch *adam(const Launch *) { return nullptr; }
     static int opt(const Launch &a) { return a.last ? 1 : 0; }
-    static void common(const Launch &a, stg::MergeBatchArgs &w) { w.sgd = a; }
-    static void fill(const Launch &a, stg::MergeTensor &d) {
+    template <class W>
+    static void common(const Launch &a, W &w) { w.sgd = a; }
+    template <class D>
+    static void fill(const Launch &a, D &d) {
         d.s0 = a.mom;
         d.s1 = a.last;
         d.u.sgd.iter = a.iter;
@@ -1440,12 +1456,14 @@ struct AdamBatch {
         *out = a;
         return STG_OK;
     }
-    static hipError_t launch(const Launch &a, hipStream_t s) { return stg::launch_adam(a, s); }
+    static hipError_t launch(const Launch &a, hipStream_t s, uint64_t *n) { return stg::launch_adam(a, s, n); }
     static const stg::SgdLaunch *sgd(const Launch *) { return nullptr; }
     static const stg::AdamLaunch *adam(const Launch *a) { return a; }
     static int opt(const Launch &) { return 2; }
-    static void common(const Launch &a, stg::MergeBatchArgs &w) { w.adam = a; }
-    static void fill(const Launch &a, stg::MergeTensor &d) {
+    template <class W>
+    static void common(const Launch &a, W &w) { w.adam = a; }
+    template <class D>
+    static void fill(const Launch &a, D &d) {
         d.s0 = a.m;
         d.s1 = a.v;
         d.u.adam.c1 = a.c1;
@@ -1456,20 +1474,22 @@ struct AdamBatch {
 // The step of a prepared call over grad_len pairs at most (none: no launch).
 template <class P>
 static int step(typename P::Launch a, const float *d_grad, const uint32_t *d_idx, uint32_t grad_len,
-                const uint32_t *d_grad_len, hipStream_t s) {
+                const uint32_t *d_grad_len, hipStream_t s, uint64_t *launches = nullptr) {
     a.grad = d_grad;
     a.gidx = d_idx;
     a.grad_len = grad_len;
     a.d_grad_len = d_grad_len;
-    if (grad_len) HIP_TRY(P::launch(a, s));
+    if (grad_len) HIP_TRY(P::launch(a, s, launches));
     return STG_OK;
 }
 
 // ... over a merge's output
 template <class P>
-static int merge_step(typename P::Handle o, const typename P::Launch &a, const MergeCall &c) {
+static int merge_step(typename P::Handle o, const typename P::Launch &a, const MergeCall &c,
+                      uint64_t *launches = nullptr) {
     const size_t cap = std::min<size_t>(c.per_rank * (size_t)c.world, P::step_cap(o, a.param_len));
-    return step<P>(a, c.out_val, c.out_idx, (uint32_t)cap, c.out_count, static_cast<hipStream_t>(c.stream));
+    return step<P>(a, c.out_val, c.out_idx, (uint32_t)cap, c.out_count, static_cast<hipStream_t>(c.stream),
+                   launches);
 }
 
 template <class P>
@@ -1514,6 +1534,9 @@ static int merge_optimize(typename P::Handle o, const char *name, float *d_param
 }
 
 // ---- the iteration's ModuleCpuOptimize tasks in one call ----
+// elements (the sum of its tensors' n) a world > 1 group may hold: two winner
+// words each, so the winner words keep MERGE_BATCH_WIN_CAP
+constexpr size_t GROUP_CAP = stg::MERGE_BATCH_WIN_CAP / 2;
 template <class P>
 static int merge_optimize_batch(typename P::Handle o, const stg_merge_task_t *tasks, size_t ntasks, void *stream) {
     if (!o) return fail(STG_ERR_INVALID, "null argument");
@@ -1526,6 +1549,7 @@ static int merge_optimize_batch(typename P::Handle o, const stg_merge_task_t *ta
     // every check of every task, before any device call or state change
     std::vector<MergeCall> calls;
     calls.reserve(ntasks);
+    // 0: the per-tensor sequence; 1: a world-1 launch pair; 2: a world > 1 group
     std::vector<uint8_t> fused(ntasks);
     for (size_t i = 0; i < ntasks; ++i) {
         const stg_merge_task_t &t = tasks[i];
@@ -1533,8 +1557,9 @@ static int merge_optimize_batch(typename P::Handle o, const stg_merge_task_t *ta
         calls.push_back(MergeCall{wire_streams(t.ranks, t.world), true, t.per_rank, t.world, t.param_len, t.d_dense,
                                   t.d_mark, t.d_out_idx, t.d_out_val, t.d_out_count, stream});
         int rc = merge_check(calls[i]);
-        fused[i] = t.world == 1 && t.per_rank > 0 && P::fuses(o);
-        if (!rc && fused[i]) rc = merge_fused_limits(calls[i], t.param_len);
+        if (t.per_rank > 0 && P::fuses(o))
+            fused[i] = t.world == 1 ? 1 : t.param_len > 0 && t.param_len <= GROUP_CAP ? 2 : 0;
+        if (!rc && fused[i] == 1) rc = merge_fused_limits(calls[i], t.param_len);
         if (!rc) rc = merge_size_check(calls[i]);
         if (rc) return refuse(i, rc);
     }
@@ -1562,6 +1587,7 @@ static int merge_optimize_batch(typename P::Handle o, const stg_merge_task_t *ta
     if (const int rc = device_cus(&ncu, &dev)) return rc;
     const std::shared_ptr<MergeScratch> ms = merge_scratch(dev, s);
     std::lock_guard<std::mutex> g(ms->mu);
+    uint64_t *const launches = &ms->launches;
     // the pending launch: tasks [g0, g0 + its count), `sum_n` winner words so far
     size_t g0 = 0, sum_n = 0;
     auto pk = stg::make_packer<stg::MergeBatchArgs>(~uint64_t(0), [&](stg::MergeBatchArgs &w, uint32_t blocks) -> int {
@@ -1574,16 +1600,85 @@ static int merge_optimize_batch(typename P::Handle o, const stg_merge_task_t *ta
         w.desc = ms->desc.get();
         w.ctl = ms->bctl.get();
         w.fail = ms->fail.get();
-        HIP_TRY(stg::launch_merge_batch(w, blocks, P::opt(L[g0]), s));
+        HIP_TRY(stg::launch_merge_batch(w, blocks, P::opt(L[g0]), s, launches));
+        return STG_OK;
+    });
+    // the pending world > 1 group: tasks [w0, w0 + its count), all of one world;
+    // `w_off` elements of dense / marks so far (slices MERGE_WORLD_ALIGN apart),
+    // `w_n` the sum of its tensors' n
+    size_t w0 = 0, w_off = 0, w_n = 0;
+    auto pw = stg::make_packer<stg::MergeWorldArgs>(GRID_MAX, [&](stg::MergeWorldArgs &w, uint32_t blocks) -> int {
+        const int world = tasks[w0].world;
+        // two tile words per tile: the counts and their prefixes
+        const int rc = merge_scratch_ensure(ms.get(), s, w_off, 0, world, 2 * (size_t)blocks, w_off);
+        w_off = w_n = 0;
+        if (rc) return rc;
+        stg::MergeScatterArgs sc{};
+        sc.nt = w.nt;
+        sc.win = ms->win.get();
+        sc.dense = ms->wdense.get();
+        sc.mark = ms->wmark.get();
+        uint64_t sblocks = 0;
+        for (uint32_t q = 0; q < w.nt; ++q) {
+            stg::MergeScatterTensor &d = sc.t[q];
+            d.m = (uint32_t)tasks[w0 + q].per_rank;
+            d.n = w.t[q].n;
+            d.off = w.t[q].off;
+            d.blk0 = (uint32_t)sblocks;
+            sblocks += (2 * (uint64_t)d.m + STG_WG - 1) / STG_WG;  // < 2^25 each
+        }
+        for (int r = 0; r <= world; ++r) {  // one launch per rank, stream-ordered: the sum's rank order
+            sc.rank = (uint32_t)r;
+            for (uint32_t q = 0; q < w.nt; ++q) {
+                const std::vector<stg::RankStream> &rs = calls[w0 + q].rs;
+                stg::MergeScatterTensor &d = sc.t[q];
+                d.sidx = r >= 1 ? rs[r - 1].idx : nullptr;
+                d.sval = r >= 1 ? rs[r - 1].val : nullptr;
+                d.sflag = r >= 1 ? rs[r - 1].flag : 0u;
+                d.midx = r < world ? rs[r].idx : nullptr;
+                d.mflag = r < world ? rs[r].flag : 0u;
+            }
+            HIP_TRY(stg::launch_merge_world_scatter(sc, (uint32_t)sblocks, s, launches));
+        }
+        w.world = (float)world;
+        w.tiles = ms->tiles.get();
+        w.dense = ms->wdense.get();
+        w.mark = ms->wmark.get();
+        HIP_TRY(stg::launch_merge_world_emit(w, blocks, P::opt(L[w0]), s, launches));
         return STG_OK;
     });
     for (size_t i = 0; i < ntasks; ++i) {
         const stg_merge_task_t &t = tasks[i];
         int rc;
+        // a change of kind closes what is pending: the call's launches keep the tasks' order
+        if (fused[i] != 1 && (rc = pk.flush())) return rc;
+        if (fused[i] != 2 && (rc = pw.flush())) return rc;
         if (!fused[i]) {  // the per-tensor sequence at its place in the order
-            if ((rc = pk.flush())) return rc;
-            if ((rc = merge_run_locked(calls[i], ms.get(), ncu, nullptr, nullptr))) return rc;
-            if ((rc = merge_step<P>(o, L[i], calls[i]))) return rc;
+            if ((rc = merge_run_locked(calls[i], ms.get(), ncu, nullptr, nullptr, launches))) return rc;
+            if ((rc = merge_step<P>(o, L[i], calls[i], launches))) return rc;
+            continue;
+        }
+        if (fused[i] == 2) {
+            // (the packer closes at MERGE_BATCH tensors; another world, the cap and a repeated name close here)
+            bool close = pw.count() && (tasks[w0].world != t.world || w_n + t.param_len > GROUP_CAP);
+            for (size_t q = w0; !close && q < w0 + pw.count(); ++q) close = strcmp(tasks[q].name, t.name) == 0;
+            if (close && (rc = pw.flush())) return rc;
+            stg::MergeWorldTensor *dp;
+            if ((rc = pw.add((t.param_len + stg::MERGE_TILE - 1) / stg::MERGE_TILE, &dp))) return rc;
+            if (pw.count() == 1) {
+                w0 = i;
+                P::common(L[i], pw.table());
+            }
+            stg::MergeWorldTensor &d = *dp;
+            d.out_idx = t.d_out_idx;
+            d.out_val = t.d_out_val;
+            d.out_count = t.d_out_count;
+            d.param = t.d_param;
+            d.n = t.param_len;
+            d.off = (uint32_t)w_off;
+            P::fill(L[i], d);
+            w_off += (t.param_len + stg::MERGE_WORLD_ALIGN - 1) / stg::MERGE_WORLD_ALIGN * stg::MERGE_WORLD_ALIGN;
+            w_n += t.param_len;
             continue;
         }
         // (the packer closes at MERGE_BATCH tensors; the winner-word cap and a repeated name close here)
@@ -1612,7 +1707,8 @@ static int merge_optimize_batch(typename P::Handle o, const stg_merge_task_t *ta
         P::fill(L[i], d);
         sum_n += t.param_len;
     }
-    return pk.flush();
+    if (const int rc = pk.flush()) return rc;
+    return pw.flush();
 }
 
 }  // namespace
@@ -1653,6 +1749,23 @@ int stg_scatter_merge_check(void *stream) {
         snprintf(b, sizeof b, "MERGE decompress device failure flags 0x%x (a look-back gave up)", f);
         return fail(STG_ERR_DEVICE, b);
     }
+    return STG_OK;
+}
+
+int stg_merge_batch_launches(void *stream, uint64_t *out) {
+    if (!out) return fail(STG_ERR_INVALID, "null argument");
+    *out = 0;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    std::shared_ptr<MergeScratch> ms;
+    {
+        std::lock_guard<std::mutex> g(g_merge_mu);
+        auto it = g_merge.find({dev, static_cast<hipStream_t>(stream)});
+        if (it == g_merge.end()) return STG_OK;  // no merge on this stream yet
+        ms = it->second;
+    }
+    std::lock_guard<std::mutex> g(ms->mu);
+    *out = ms->launches;
     return STG_OK;
 }
 

@@ -56,56 +56,8 @@ __global__ void __launch_bounds__(STG_WG) merge_mark_batch(MergeBatchArgs w) {
     }
 }
 
-// One winner's optimizer step: the per-tensor kernels' sgd_step / adam_step on
-// the launch structure rebuilt from the handle-wide scalars and the tensor's
-// fields.
-template <int OPT>
-struct Step;
-template <>
-struct Step<2> {
-    AdamLaunch a;
-    __device__ __forceinline__ Step(const MergeBatchArgs &w, const MergeTensor &d) : a(w.adam) {
-        a.param = d.param;
-        a.param_len = d.n;
-        a.m = d.s0;
-        a.v = static_cast<float *>(d.s1);
-        a.c1 = d.u.adam.c1;
-        a.c2 = d.u.adam.c2;
-    }
-    __device__ __forceinline__ void load(uint32_t id, float &x, float &m, float &v, uint32_t &l) const {
-        x = a.param[id];
-        m = a.m[id];
-        v = a.v[id];
-        l = 0u;
-    }
-    __device__ __forceinline__ void factors(float &, uint32_t) const {}
-    __device__ __forceinline__ void step(uint32_t id, float g, float x, float m, float v, uint32_t) const {
-        adam_step(a, id, g, x, m, v);
-    }
-};
-template <int OPT>
-struct Step {
-    static constexpr bool SMART = OPT == 1;
-    SgdLaunch a;
-    __device__ __forceinline__ Step(const MergeBatchArgs &w, const MergeTensor &d) : a(w.sgd) {
-        a.param = d.param;
-        a.param_len = d.n;
-        a.mom = d.s0;
-        a.last = static_cast<uint32_t *>(d.s1);
-        a.iter = d.u.sgd.iter;
-        a.first = d.u.sgd.first != 0;
-    }
-    __device__ __forceinline__ void load(uint32_t id, float &x, float &m, float &, uint32_t &l) const {
-        x = a.param[id];
-        m = a.mom ? a.mom[id] : 0.f;
-        l = SMART ? a.last[id] : 0u;
-    }
-    // SMART: the winners' factors, gathered from the table together (else the momentum)
-    __device__ __forceinline__ void factors(float &f, uint32_t l) const { f = sgd_factor<SMART>(a, l); }
-    __device__ __forceinline__ void step(uint32_t id, float g, float x, float m, float f, uint32_t l) const {
-        sgd_step<SMART>(a, id, g, x, m, f, l);
-    }
-};
+// (One winner's optimizer step, Step<OPT>: merge_dev.h, shared with
+// merge_batch_world.hip.)
 
 // win_emit1t<4, SMART, true> per tensor of the group (apply.hip): tiles in the
 // tensor's own ticket order, tagged tile counts in its own desc slice, the
@@ -240,8 +192,9 @@ __global__ void __launch_bounds__(STG_WG) merge_emit_batch(MergeBatchArgs w) {
 
 }  // namespace
 
-hipError_t launch_merge_batch(const MergeBatchArgs &w, uint32_t blocks, int opt, hipStream_t s) {
+hipError_t launch_merge_batch(const MergeBatchArgs &w, uint32_t blocks, int opt, hipStream_t s, uint64_t *launches) {
     if (!w.nt || !blocks) return hipSuccess;
+    count_launch(launches, 2);  // the election and the emission
     merge_mark_batch<<<blocks, STG_WG, 0, s>>>(w);
     if (opt == 2) merge_emit_batch<2><<<blocks, STG_WG, 0, s>>>(w);
     else if (opt == 1) merge_emit_batch<1><<<blocks, STG_WG, 0, s>>>(w);

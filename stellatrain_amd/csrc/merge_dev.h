@@ -1,7 +1,7 @@
 // merge_dev.h -- per-element device code of the MERGE decompress emission and
 // the optimizer steps fused into it, shared by the per-tensor kernels
-// (apply.hip) and the batched ones (merge_batch.hip): one text, so the two
-// agree bitwise.  gfx950 only.
+// (apply.hip) and the batched ones (merge_batch.hip, merge_batch_world.hip):
+// one text, so they agree bitwise.  gfx950 only.
 #pragma once
 
 #include <algorithm>
@@ -105,6 +105,81 @@ __device__ __forceinline__ void adam_step(const AdamLaunch &a, uint32_t id, floa
     a.param[id] = (float)((double)x - num / ((double)a.eps + sqrt(vt_hat)));
     a.m[id] = mt;
     a.v[id] = vt;
+}
+
+// One emitted pair's optimizer step in a batched launch: sgd_step / adam_step
+// on the launch structure rebuilt from the handle-wide scalars of the launch's
+// table `w` (w.sgd / w.adam) and the tensor's fields `d` (param, n, s0, s1, u:
+// MergeTensor, MergeWorldTensor).  OPT: 0 = SGD, 1 = SGD with smart momentum,
+// 2 = Adam (no amsgrad).
+template <int OPT>
+struct Step;
+template <>
+struct Step<2> {
+    AdamLaunch a;
+    template <class W, class D>
+    __device__ __forceinline__ Step(const W &w, const D &d) : a(w.adam) {
+        a.param = d.param;
+        a.param_len = d.n;
+        a.m = d.s0;
+        a.v = static_cast<float *>(d.s1);
+        a.c1 = d.u.adam.c1;
+        a.c2 = d.u.adam.c2;
+    }
+    __device__ __forceinline__ void load(uint32_t id, float &x, float &m, float &v, uint32_t &l) const {
+        x = a.param[id];
+        m = a.m[id];
+        v = a.v[id];
+        l = 0u;
+    }
+    __device__ __forceinline__ void factors(float &, uint32_t) const {}
+    __device__ __forceinline__ void step(uint32_t id, float g, float x, float m, float v, uint32_t) const {
+        adam_step(a, id, g, x, m, v);
+    }
+};
+template <int OPT>
+struct Step {
+    static constexpr bool SMART = OPT == 1;
+    SgdLaunch a;
+    template <class W, class D>
+    __device__ __forceinline__ Step(const W &w, const D &d) : a(w.sgd) {
+        a.param = d.param;
+        a.param_len = d.n;
+        a.mom = d.s0;
+        a.last = static_cast<uint32_t *>(d.s1);
+        a.iter = d.u.sgd.iter;
+        a.first = d.u.sgd.first != 0;
+    }
+    __device__ __forceinline__ void load(uint32_t id, float &x, float &m, float &, uint32_t &l) const {
+        x = a.param[id];
+        m = a.mom ? a.mom[id] : 0.f;
+        l = SMART ? a.last[id] : 0u;
+    }
+    // SMART: the winners' factors, gathered from the table together (else the momentum)
+    __device__ __forceinline__ void factors(float &f, uint32_t l) const { f = sgd_factor<SMART>(a, l); }
+    __device__ __forceinline__ void step(uint32_t id, float g, float x, float m, float f, uint32_t l) const {
+        sgd_step<SMART>(a, id, g, x, m, f, l);
+    }
+};
+
+// world > 1: a lane's 16 mark bytes at e (one 16-byte load where all exist;
+// the array starts 16-byte aligned and e % 16 == 0), and how many bytes of a
+// word of them are set.
+__device__ __forceinline__ uint32_t nz_bytes(uint32_t w) {
+    uint32_t c = 0;
+    c += (w & 0xffu) != 0;
+    c += (w & 0xff00u) != 0;
+    c += (w & 0xff0000u) != 0;
+    c += (w & 0xff000000u) != 0;
+    return c;
+}
+
+__device__ __forceinline__ uint4 load_marks(const uint8_t *mark, size_t n, size_t e) {
+    if (e + 16 <= n) return *reinterpret_cast<const uint4 *>(mark + e);
+    uint32_t w[4] = {0, 0, 0, 0};
+    for (uint32_t b = 0; b < 16; ++b)
+        if (e + b < n) w[b >> 2] |= (uint32_t)mark[e + b] << (8 * (b & 3));
+    return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
 }  // namespace stg

@@ -367,6 +367,12 @@ struct Win1Desc {
     const struct AdamLaunch *adam = nullptr;  // ... or the Adam step (no amsgrad)
 };
 constexpr uint32_t MERGE_TILE = STG_WG * 16;  // pairs / marks per scatter-merge tile
+// `launches` of the MERGE and step launchers below: where given, the kernel
+// launches enqueued are added to it as they are enqueued (the batched entries'
+// counter, stg_merge_batch_launches).
+inline void count_launch(uint64_t *launches, uint32_t k = 1) {
+    if (launches) *launches += k;
+}
 // MERGE decompress of `world` rank streams of per_rank pairs each, every one
 // read where it landed, in the form its flag says it arrived in (STG_WIRE_*
 // bits; wire_dev.h).  Flag 0 is the decoded form (u32 / f32) and takes the
@@ -378,7 +384,7 @@ struct RankStream {
 hipError_t launch_scatter_merge(const RankStream *ranks, size_t per_rank, int world, size_t n, float *dense,
                                 uint8_t *mark, uint32_t *out_idx, float *out_val, uint32_t *out_count,
                                 uint32_t *scratch_tiles, uint32_t *win, int num_cu, hipStream_t s,
-                                const Win1Desc &w1);
+                                const Win1Desc &w1, uint64_t *launches = nullptr);
 
 struct SgdLaunch {
     float *param;
@@ -401,7 +407,7 @@ struct SgdLaunch {
     uint32_t *fail;        // sticky failure word of the optimizer handle (SGD_FAIL_FACTOR)
 };
 constexpr uint32_t SGD_FAIL_FACTOR = 1u;  // a factor outside [0, 1): an index repeated within one call
-hipError_t launch_sgd(const SgdLaunch &a, hipStream_t s);
+hipError_t launch_sgd(const SgdLaunch &a, hipStream_t s, uint64_t *launches = nullptr);
 
 struct AdamLaunch {
     float *param;
@@ -420,7 +426,7 @@ struct AdamLaunch {
     bool amsgrad, maximize;
 };
 constexpr uint32_t ADAM_TILE = STG_WG * 4;  // amsgrad: elements per workgroup tile
-hipError_t launch_adam(const AdamLaunch &a, hipStream_t s);
+hipError_t launch_adam(const AdamLaunch &a, hipStream_t s, uint64_t *launches = nullptr);
 
 // Batched world-1 MERGE decompress + fused optimizer step (merge_batch.hip):
 // one election launch and one emission launch for up to MERGE_BATCH tensors.
@@ -473,7 +479,69 @@ struct MergeBatchArgs {
 static_assert(sizeof(MergeBatchArgs) <= 2048, "kernel arguments: stay well under 4 KiB");
 // opt: 0 = SGD, 1 = SGD with smart momentum, 2 = Adam (no amsgrad); blocks =
 // the sum of the tensors' tiles
-hipError_t launch_merge_batch(const MergeBatchArgs &w, uint32_t blocks, int opt, hipStream_t s);
+hipError_t launch_merge_batch(const MergeBatchArgs &w, uint32_t blocks, int opt, hipStream_t s,
+                              uint64_t *launches = nullptr);
+
+// Batched world > 1 MERGE decompress + fused optimizer step
+// (merge_batch_world.hip): up to MERGE_BATCH tensors of one world share
+// world + 1 scatter launches, the mark count, its scan and the emission.  A
+// tensor works on its own slices of the (device, stream) scratch, which start
+// at `off` elements (a multiple of 16, so every slice is 16-byte aligned):
+// dense floats and mark bytes at off, its 2 n winner words at 2 off.  The sum
+// of a group's n stays at MERGE_BATCH_WIN_CAP / 2, so the winner words keep
+// the 32 MiB bound above (16 MiB of dense, 4 MiB of marks).
+constexpr uint32_t MERGE_WORLD_ALIGN = 16;  // elements between slice starts: a multiple of this
+struct MergeScatterTensor {
+    const void *sidx, *sval;  // the rank this launch scatters (null: none, the first launch)
+    const void *midx;         // the rank it elects (null: none, the last launch)
+    uint32_t sflag, mflag;
+    uint32_t m, n;            // pairs per rank; parameter length
+    uint32_t blk0;            // first workgroup of this tensor (STG_WG threads over 2 m)
+    uint32_t off;
+};
+struct MergeScatterArgs {
+    MergeScatterTensor t[MERGE_BATCH];
+    uint32_t nt;
+    uint32_t rank;            // the launch: scatters rank - 1, elects rank
+    uint32_t *win;
+    float *dense;
+    uint8_t *mark;
+};
+struct MergeWorldTensor {
+    uint32_t *out_idx;
+    float *out_val;
+    uint32_t *out_count;
+    float *param;
+    float *s0;                // as MergeTensor's
+    void *s1;
+    union {
+        struct { double c1, c2; } adam;
+        struct { uint32_t iter, first; } sgd;
+    } u;
+    uint32_t n;               // parameter length
+    uint32_t blk0;            // first workgroup (= MERGE_TILE tile) in the count and the emission;
+                              // its 2 * tiles tile words start at 2 * blk0
+    uint32_t off;
+    uint32_t pad;
+};
+struct MergeWorldArgs {
+    MergeWorldTensor t[MERGE_BATCH];
+    uint32_t nt;
+    float world;
+    uint32_t *tiles;
+    float *dense;
+    uint8_t *mark;
+    SgdLaunch sgd;            // the handle-wide scalars (per-tensor fields unset), opt 0 / 1
+    AdamLaunch adam;          // ... opt 2
+};
+static_assert(sizeof(MergeScatterArgs) <= 2048 && sizeof(MergeWorldArgs) <= 2048,
+              "kernel arguments: stay well under 4 KiB");
+// launch `w.rank` of a group's world + 1 (blocks = the sum over its tensors of ceil(2 m / STG_WG))
+hipError_t launch_merge_world_scatter(const MergeScatterArgs &w, uint32_t blocks, hipStream_t s,
+                                      uint64_t *launches = nullptr);
+// the mark count, its scan and the emission with the step (opt as above; blocks = the sum of the tensors' tiles)
+hipError_t launch_merge_world_emit(const MergeWorldArgs &w, uint32_t blocks, int opt, hipStream_t s,
+                                   uint64_t *launches = nullptr);
 hipError_t launch_gather_add(const GatherArgs &a, size_t start, size_t end, int num_cu, hipStream_t s);
 constexpr uint32_t WIRE_BATCH = 16;  // buckets per batched wire launch
 struct WireBucket {

@@ -24,7 +24,7 @@ from ._capi import CodecError, StgMergeTask, StgRankStream, StgWireRx, check, li
 from .compressor import Compressor, make_compressor
 
 __all__ = ["CodecEngine", "SparseSGD", "MergeTasks", "merge_numel", "api_numel", "scatter_merge", "scatter_merge_wire",
-           "wire_decode_batch", "owner_of"]
+           "wire_decode_batch", "owner_of", "merge_batch_launches"]
 
 
 def merge_numel(n: int, ratio: float, world: int = 1) -> int:
@@ -192,6 +192,22 @@ def scatter_merge_release(device=None) -> None:
     dev = _cuda_device(device)
     with torch.cuda.device(dev):
         check(lib().stg_scatter_merge_release(C.c_void_p(torch.cuda.current_stream(dev.index).cuda_stream)))
+
+
+def merge_batch_launches(device=None) -> int:
+    """Kernel launches the ``merge_optimize_batch`` calls have enqueued on the
+    current stream of ``device`` since its MERGE scratch was created (0 before
+    the first merge on it, and again after ``scatter_merge_release``): the
+    shared launches and the per-tensor sequences run inside a batch, their
+    step launches included.  A batched call's results are those of the loop;
+    the difference of this count around a call shows what it shared."""
+    import torch
+    dev = _cuda_device(device)
+    out = C.c_uint64()
+    with torch.cuda.device(dev):
+        check(lib().stg_merge_batch_launches(C.c_void_p(torch.cuda.current_stream(dev.index).cuda_stream),
+                                             C.byref(out)))
+    return int(out.value)
 
 
 def _cuda_device(device):
@@ -405,9 +421,10 @@ class MergeTasks:
     out_val, count`` (positional, None to allocate); ``streams`` is a list of
     (widx, wval, flag) as in ``scatter_merge_wire``, validated as there.
     ``outputs`` holds one (out_idx, out_val, count) per item: every call on
-    the array writes the same output tensors (and, at world > 1, uses the same
-    dense / mark scratch, left zero by each call), so read an iteration's
-    merged streams before the next call.  The array keeps every tensor it
+    the array writes the same output tensors (and, at world > 1, is given the
+    same dense / mark scratch, left zero by each call; items that share a group
+    work on the library's scratch instead), so read an iteration's merged
+    streams before the next call.  The array keeps every tensor it
     points at alive, the ones allocated here included."""
 
     def __init__(self, items):
@@ -553,9 +570,14 @@ class SparseSGD:
         are ``(param, name, streams, per_rank[, dense, mark, out_idx, out_val,
         count])``; bitwise the results of the loop.  Consecutive world-1 items
         (up to 16, parameter lengths summing to at most 8 Mi, distinct names)
-        share one launch pair; world > 1 and empty items run one by one at
-        their place.  ``items`` may be a prebuilt ``MergeTasks`` (no per-call
-        marshalling).  Returns a list of (out_idx, out_val, count)."""
+        share one launch pair.  Consecutive items of one world > 1 (up to 16,
+        parameter lengths summing to at most 4 Mi, distinct names) share
+        world + 4 launches and work on the library's scratch; their ``dense``
+        / ``mark`` are still required, stay zero, and one pair may serve every
+        item.  Empty items and world > 1 items above 4 Mi elements run one by
+        one at their place.  ``items`` may be a prebuilt ``MergeTasks`` (no
+        per-call marshalling).  Returns a list of (out_idx, out_val, count).
+        ``merge_batch_launches`` counts the launches."""
         return _merge_optimize_batch(lib().stg_merge_optimize_sgd_batch_device, self._h, items)
 
     def momentum_buffer(self, name: str, n: int):

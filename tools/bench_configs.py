@@ -619,32 +619,52 @@ def batch_merge(torch, repeats=7):
     reported; the batch both marshalled from tensors on every call and from a
     prebuilt MergeTasks (wall clock: both are host- and launch-bound).  (a) 256 tensors of
     n = 60,000, k = 600 at wire flag 0 and 1; (b) the first 256 sizes of the C4
-    list at k = 1 %, flag 0.  A tensor's indices are one per stride of n / k,
-    each at a random place in its stride: distinct and sorted."""
+    list at k = 1 %, flag 0; (c) the set of (a) at flag 1 with world 2 and 8
+    rank streams per tensor (groups of 16 tensors sharing world + 4 launches),
+    one dense / mark pair for all tasks.  A rank's indices are one per stride of
+    n / k, each at a random place in its stride: distinct and sorted.  Rows
+    carry the launches the batched call enqueued (merge_batch_launches) where
+    the library counts them."""
     from stellatrain_amd import MergeTasks, merge_numel, wire_encode
     from stellatrain_amd.shard import c4_sizes
     dev = torch.device("cuda", 0)
     repeats = max(5, repeats)
     out = []
     gen = torch.Generator(device="cpu").manual_seed(23)
-    for label, sizes, flag in (("256 tensors n=60000", [60000] * 256, 0), ("256 tensors n=60000", [60000] * 256, 1),
-                               ("first 256 sizes of the C4 list", c4_sizes()[:256], 0)):
+    try:
+        from stellatrain_amd import merge_batch_launches
+    except ImportError:  # a library from before the counter
+        merge_batch_launches = None
+    for label, sizes, flag, world in (("256 tensors n=60000", [60000] * 256, 0, 1),
+                                      ("256 tensors n=60000", [60000] * 256, 1, 1),
+                                      ("first 256 sizes of the C4 list", c4_sizes()[:256], 0, 1),
+                                      ("256 tensors n=60000", [60000] * 256, 1, 2),
+                                      ("256 tensors n=60000", [60000] * 256, 1, 8)):
         tasks = []
+        dense = mark = None
+        if world > 1:
+            dense = torch.zeros(max(sizes), dtype=torch.float32, device=dev)
+            mark = torch.zeros(max(sizes), dtype=torch.uint8, device=dev)
         for j, n in enumerate(sizes):
             k = merge_numel(n, 0.99)
             stride = n // k
-            idx = (torch.arange(k, dtype=torch.int64) * stride + torch.randint(0, stride, (k,), generator=gen))
-            wi, wv = wire_encode(idx.to(torch.int32).to(dev), torch.randn(k, generator=gen).to(dev), flag)
-            tasks.append((torch.zeros(n, dtype=torch.float32, device=dev), f"{j}@w", [(wi, wv, flag)], k,
-                          torch.empty(k, dtype=torch.int32, device=dev), torch.empty(k, dtype=torch.float32, device=dev),
+            rs = []
+            for _ in range(world):
+                idx = (torch.arange(k, dtype=torch.int64) * stride + torch.randint(0, stride, (k,), generator=gen))
+                wi, wv = wire_encode(idx.to(torch.int32).to(dev), torch.randn(k, generator=gen).to(dev), flag)
+                rs.append((wi, wv, flag))
+            tasks.append((torch.zeros(n, dtype=torch.float32, device=dev), f"{j}@w", rs, k,
+                          torch.empty(k * world, dtype=torch.int32, device=dev),
+                          torch.empty(k * world, dtype=torch.float32, device=dev),
                           torch.empty(1, dtype=torch.int32, device=dev)))
-        items = [(p, nm, rs, k, None, None, oi, ov, oc) for p, nm, rs, k, oi, ov, oc in tasks]
+        dm = lambda n: (dense[:n], mark[:n]) if world > 1 else (None, None)  # noqa: E731
+        items = [(p, nm, rs, k) + dm(p.numel()) + (oi, ov, oc) for p, nm, rs, k, oi, ov, oc in tasks]
         loop_opt, _ = make_opt("sgd")
         batch_opt, _ = make_opt("sgd")
 
         def loop():
             for p, nm, rs, k, oi, ov, oc in tasks:
-                loop_opt.merge_optimize_wire(p, nm, rs, k, None, None, oi, ov, oc)
+                loop_opt.merge_optimize_wire(p, nm, rs, k, *dm(p.numel()), oi, ov, oc)
 
         def batch():
             batch_opt.merge_optimize_batch(items)
@@ -662,10 +682,16 @@ def batch_merge(torch, repeats=7):
                 if r >= 2:
                     t[name].append((time.perf_counter() - t0) * 1e6)
         union = sum(int(x[6].item()) for x in tasks)  # u16 indices: the saturated repeats merge
-        assert 0 < union <= sum(x[3] for x in tasks)
+        assert 0 < union <= sum(x[3] for x in tasks) * world
+        launches = None
+        if merge_batch_launches is not None:
+            before = merge_batch_launches()
+            batch_pre()
+            launches = merge_batch_launches() - before
         lo, ba, pr = (float(np.median(t[x])) for x in ("loop", "batch", "pre"))
-        out.append({"config": f"BMERGE merge_optimize SGD(m=0.9), {label}, k=1%, wire flag {flag}, world=1",
+        out.append({"config": f"BMERGE merge_optimize SGD(m=0.9), {label}, k=1%, wire flag {flag}, world={world}",
                     "tensors": len(sizes), "floats": int(sum(sizes)), "union": union, "repeats": repeats,
+                    "batch_launches": launches,
                     "loop_us": round(lo, 1), "batch_us": round(ba, 1), "loop_over_batch": round(lo / ba, 2),
                     "batch_prebuilt_us": round(pr, 1), "loop_over_prebuilt": round(lo / pr, 2),
                     "loop_us_min_max": [round(min(t["loop"]), 1), round(max(t["loop"]), 1)],
