@@ -297,7 +297,14 @@ __global__ void __launch_bounds__(TWG, 8) tv_pass(TvArgs a) {
     // the last range has seen every range's count (the look-back), and each
     // range stored its maximum before its count: fold them
     if (r != G - 1) return;
-    uint32_t gm = 0;
+    // The reference folds gmax = (a < gmax) ? gmax : a in element order
+    // (thresholdv.cpp), which a NaN restarts: the result is the maximum of
+    // the elements after the bucket's last NaN, or that NaN when it is the
+    // last element.  A range's maximum of magnitude bits is above inf's
+    // exactly when the range holds a NaN, so the fold also finds the last
+    // such range; only then is that one range read again below.
+    constexpr uint32_t INF_BITS = 0x7f800000u;
+    uint32_t gm = 0, hn = 0;  // hn: 1 + the last range with a NaN
     for (uint32_t i = tid; i < G; i += TWG) {  // every range's tagged maximum
         uint64_t x = ld_sc1(&a.rmax[i]);
         uint64_t st = 0;
@@ -307,11 +314,37 @@ __global__ void __launch_bounds__(TWG, 8) tv_pass(TvArgs a) {
             if (spin_expired(spins, st)) { g_or(a.fail, FAIL_SPIN_TIMEOUT); break; }
         }
         gm = max(gm, (uint32_t)x);
+        if ((uint32_t)x > INF_BITS) hn = max(hn, i + 1u);
     }
     const uint64_t cntall = P + c;
     gm = wave_max(gm);
-    if (lane == 0) s_max[wave] = gm;
+    hn = wave_max(hn);
+    if (lane == 0) { s_max[wave] = gm; s_cnt[wave] = hn; }
     __syncthreads();
+    uint32_t hn_all = 0;
+    for (uint32_t i = 0; i < TNW; ++i) hn_all = max(hn_all, s_cnt[i]);
+    __syncthreads();
+    if (hn_all) {  // rare and uniform: a NaN somewhere in the bucket
+        const uint32_t rn = hn_all - 1u;
+        const TvRange Rn = tv_range(n4, G, rn);
+        const uint64_t e0 = Rn.lo * 4, e1 = rn == G - 1 ? n : (Rn.lo + Rn.len) * 4;  // (the last range has the ragged tail)
+        uint32_t pl = 0;  // 1 + the range's last NaN element (a range holds < 2^30 floats)
+        for (uint64_t e = e0 + tid; e < e1; e += TWG)
+            if (f2u(fabsf(a.src[e])) > INF_BITS) pl = (uint32_t)(e - e0) + 1u;
+        pl = wave_max(pl);
+        if (lane == 0) s_cnt[wave] = pl;
+        __syncthreads();
+        uint32_t pl_all = 0;
+        for (uint32_t i = 0; i < TNW; ++i) pl_all = max(pl_all, s_cnt[i]);
+        const uint64_t pn = e0 + pl_all - 1u;  // the bucket's last NaN (pl_all >= 1: the range's maximum said so)
+        gm = 0;
+        for (uint64_t e = pn + 1 + tid; e < e1; e += TWG) gm = max(gm, f2u(fabsf(a.src[e])));
+        for (uint32_t i = rn + 1 + tid; i < G; i += TWG) gm = max(gm, (uint32_t)ld_sc1(&a.rmax[i]));
+        if (pl_all && pn + 1 == n) gm = f2u(fabsf(a.src[pn]));  // ends in a NaN: that NaN
+        gm = wave_max(gm);
+        if (lane == 0) s_max[wave] = gm;
+        __syncthreads();
+    }
     if (tid == 0) {
         uint32_t g = 0;
         for (uint32_t i = 0; i < TNW; ++i) g = max(g, s_max[i]);

@@ -527,6 +527,19 @@ __device__ void full_path(FillLds &S, const Tv16FillBucket d, uint32_t cnt, uint
     emit_order(d, cnt, rem, np, tail_rank, [&](uint32_t i) { return hld(H, N - 1 - i).y; });
 }
 
+// The crew's call of it (tv16wide.h), never inlined.  Inlined into the batched
+// crew loop, the compiler spilled the partial line's lane test under the
+// one-lane exec mask of make_heap's last level, and the last popped line lost
+// every fourth element.  Seen with hipcc 7.2 (AMD clang
+// 22.0.0git, roc-7.2.0); tests/test_gpu_edge_values.py
+// test_thresholdv16_edge_batch fails without this and is what to run again,
+// with a look at the assembly for a spill ahead of a block's exec restore,
+// after a change of compiler or of this file's register pressure.
+__device__ __attribute__((noinline)) void full_path_crew(FillLds &S, const Tv16FillBucket &d, uint32_t cnt, uint32_t N,
+                                                         float t, bool tail, float tail_key, uint32_t *fail) {
+    full_path(S, d, cnt, N, t, tail, tail_key, fail);
+}
+
 #include "tv16lfin.h"
 #include "tv16wide.h"
 
@@ -654,7 +667,7 @@ tv16_fill(Tv16FillArgs A) {
         }
         const uint64_t h1 = ld_sc1(&D.w[1]);
         if ((uint32_t)(h0 >> 32) != ((A.epoch << 8) | TV16_TAG_DEC) || !((uint32_t)h0 & TV16_DEC_B) ||
-            ld_sc1(A.fail) || share > A.helpers || (A.crew && crew_wants((uint32_t)h0, (uint32_t)h1, A.mode)))
+            ld_sc1(A.fail) || share > A.helpers || (A.crew && crew_wants((uint32_t)h0, (uint32_t)h1, A.mode, (uint32_t)ld_sc1(&D.w[2]))))
             return;  // no regime-B fill (or the scan failed, or the crew orders it): nothing to emit
         if (!(uint32_t)h1 && !((uint32_t)h0 & TV16_DEC_TAIL)) return;  // nothing missing (the orderer returns too)
         uint64_t st0 = 0;
@@ -730,14 +743,15 @@ tv16_fill(Tv16FillArgs A) {
     const uint32_t N = d.nb - Qtot + (tail ? 1u : 0u);  // candidate vector length
     const uint32_t rem = d.dst_len - cnt;
     if (!M && !tail) return;
-    if (A.crew && crew_wants(flags, M, A.mode)) return;  // a window miss: the crew orders it (tv16wide.h)
+    if (A.crew && crew_wants(flags, M, A.mode, (uint32_t)w2)) return;  // a window miss: the crew orders it (tv16wide.h)
     const uint32_t nhelp = LONE ? A.helpers : 0u;
     CallCtl *const ccp = A.cc;
     const uint32_t tb = f2u(t);
     const uint32_t wlo = tb > TV16_WIN ? tb - TV16_WIN : 0u;
     const bool tail_in = tail && tail_key >= u2f(wlo);
+    const bool tail_nan = nan_tail(flags, (uint32_t)w2);  // the literal heap's (tv16wide.h nan_tail)
     bool fast = (flags & TV16_DEC_WIN) && N <= POS_LIM && Wtot + (tail_in ? 1u : 0u) > 0 && A.mode != 2u &&
-                A.mode != 3u;
+                A.mode != 3u && !tail_nan;
     if (!fast && tid == 0) {  // why the literal heap (debug words 60..63)
         if (!(flags & TV16_DEC_WIN)) atomicAdd(&A.dbg[60], 1u);
         if (N > POS_LIM) atomicAdd(&A.dbg[61], 1u);
@@ -1210,7 +1224,7 @@ tv16_fill(Tv16FillArgs A) {
     __syncthreads();
     // the leader (tv16wide.h) over the window list, when the window holds the
     // top min(P0 + 2, N) candidates (the ragged tail joins as an entry)
-    if ((flags & TV16_DEC_WIN) && A.mode != 2u) {
+    if ((flags & TV16_DEC_WIN) && A.mode != 2u && !tail_nan) {
         const uint32_t P0 = (rem + 15u) / 16u, seln = min(P0 + 1u, N - 1u);
         if (Wtot >= seln + 1u || Wtot + (tail ? 1u : 0u) == N) {
             WideLds &Wl = *reinterpret_cast<WideLds *>(fill_lds);

@@ -367,7 +367,8 @@ __device__ __forceinline__ bool lf2_ranker(Lf2Lds &L, uint32_t rk) {
     // (the conditions of lfin_ranker; a -0.0 tail ties +0.0 sums in the
     // reference's float compare, not in this key order; prefixes fit u16)
     if (!D.listw || !D.lists_ok || D.N > LF2_POS_LIM || W == 0 || A.mode || D.Qtot > 0xffffu ||
-        (tail_in && (f2u(D.tail_key) & 0x80000000u)) || (tail_in && !(D.tail_key < D.t)))
+        (tail_in && (f2u(D.tail_key) & 0x80000000u)) || (tail_in && !(D.tail_key < D.t)) ||
+        (D.tail_cand && D.tail_key != D.tail_key))  // (a NaN tail: tv16wide.h nan_tail)
         return fail_at(1);
     const uint32_t tw = tail_in ? tb - 1u - f2u(D.tail_key) : 0u, tbin = tail_in ? tw >> 8 : LF2_NONE;
     const uint32_t need = D.M + 2, rem = A.dst_len - D.cnt;

@@ -374,7 +374,7 @@ __device__ __noinline__ void lfin_ranker(LfinLds &L, uint32_t rk) {
     const uint32_t W = D.Wtot + (tail_in ? 1u : 0u);
     // a -0.0 tail ties +0.0 sums in the reference's float compare, not in ford() order
     if (!D.listw || !D.lists_ok || D.N > POS_LIM || W == 0 || A.mode ||
-        (tail_in && (f2u(D.tail_key) & 0x80000000u))) {
+        (tail_in && (f2u(D.tail_key) & 0x80000000u)) || (D.tail_cand && D.tail_key != D.tail_key)) {  // (a NaN tail: tv16wide.h nan_tail)
         give_up();
         return;
     }

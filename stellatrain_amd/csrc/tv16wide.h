@@ -724,9 +724,16 @@ __device__ __noinline__ LeadOut leader(WL &W, const LeadIn I) {
 // the crew
 // ---------------------------------------------------------------------------
 // regime B with lines (or the tail) to fill, and the window does not hold them
-__device__ __forceinline__ bool crew_wants(uint32_t flags, uint32_t M, uint32_t mode) {
+// A ragged tail whose signed sum is NaN joins the reference's heap under a
+// comparator that is then always false: only the literal heap reproduces what
+// make_heap / pop_heap do with it (with 2^m - 1 candidates it climbs from the
+// last leaf to the root and pops first), so every other way declines it.
+__device__ __forceinline__ bool nan_tail(uint32_t flags, uint32_t tail_bits) {
+    return (flags & TV16_DEC_TAIL) && (tail_bits & 0x7fffffffu) > 0x7f800000u;
+}
+__device__ __forceinline__ bool crew_wants(uint32_t flags, uint32_t M, uint32_t mode, uint32_t tail_bits) {
     return (flags & TV16_DEC_B) && (M || (flags & TV16_DEC_TAIL)) && (!(flags & TV16_DEC_WIN) || mode == 4u) &&
-           mode != 2u;  // mode 2 (tests): the literal heap for every regime-B bucket
+           mode != 2u && !nan_tail(flags, tail_bits);  // mode 2 (tests): the literal heap for every regime-B bucket
 }
 
 // scratch layout of a crew bucket (words of d.heap: 2 (nb + 64) of them)
@@ -1021,7 +1028,7 @@ __device__ __noinline__ void crew_loop(WL &W, FillLds &S, const CrewArgs A) {
             if (!ok) {  // exact, slow; its LDS view covers this workgroup's plan, so it takes no more units (uniform: the leader's result)
                 const CrewBk Bl = B;
                 __syncthreads();
-                full_path(S, Bl.d, Bl.cnt, Bl.N, u2f(Bl.tbits), Bl.tail != 0, u2f(Bl.tail_bits), A.fail);
+                full_path_crew(S, Bl.d, Bl.cnt, Bl.N, u2f(Bl.tbits), Bl.tail != 0, u2f(Bl.tail_bits), A.fail);
                 vm_drain();
                 __syncthreads();
                 if (tid == 0) g_add(&done[p], 1u);
@@ -1088,7 +1095,7 @@ __device__ __forceinline__ void crew_from_decisions(WideLds &W, FillLds &S, cons
             if ((uint32_t)(w0 >> 32) != ((A.epoch << 8) | TV16_TAG_DEC)) continue;
             const uint64_t w1 = ld_sc1(&Dc.w[1]), w2 = ld_sc1(&Dc.w[2]), w3 = ld_sc1(&Dc.w[3]);
             const uint32_t flags = (uint32_t)w0;
-            if (!crew_wants(flags, (uint32_t)w1, A.mode)) continue;
+            if (!crew_wants(flags, (uint32_t)w1, A.mode, (uint32_t)w2)) continue;
             CrewBk &B = W.bk[nr++];
             B.d = A.bk[b];
             B.slot = b;
@@ -1114,7 +1121,7 @@ __device__ __forceinline__ void crew_lfin(LfinLds &Lf, const Tv16FillArgs &A) {
     lfin_prefix(Lf, Lf.args, D);
     const uint32_t flags =
         D.regimeB ? (TV16_DEC_B | (D.tail_cand ? TV16_DEC_TAIL : 0u) | (D.listw ? TV16_DEC_WIN : 0u)) : 0u;
-    const bool want = crew_wants(flags, D.M, A.mode) && !ld_sc1(A.fail);
+    const bool want = crew_wants(flags, D.M, A.mode, f2u(D.tail_key)) && !ld_sc1(A.fail);
     __syncthreads();  // every read of the lfin view is done
     WideLdsBig &W = *reinterpret_cast<WideLdsBig *>(&Lf);
     if (threadIdx.x == 0) {
