@@ -130,10 +130,16 @@ class Oracle(_Codecs):
         lib.orc_sgd_new.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int]
         lib.orc_sgd_free.restype = None
         lib.orc_sgd_free.argtypes = [C.c_void_p]
-        lib.orc_sgd_apply.restype = None
+        lib.orc_sgd_apply.restype = C.c_int
         lib.orc_sgd_apply.argtypes = [C.c_void_p, C.c_char_p, _f32p, C.c_uint32, _f32p, _u32p, C.c_uint32]
         lib.orc_sgd_momentum.restype = C.c_int
         lib.orc_sgd_momentum.argtypes = [C.c_void_p, C.c_char_p, _f32p, C.c_uint32]
+        lib.orc_sgd_smart.restype = None
+        lib.orc_sgd_smart.argtypes = [C.c_void_p, C.c_int]
+        lib.orc_sgd_iter.restype = C.c_uint32
+        lib.orc_sgd_iter.argtypes = [C.c_void_p]
+        lib.orc_sgd_last.restype = C.c_int
+        lib.orc_sgd_last.argtypes = [C.c_void_p, C.c_char_p, _u32p, C.c_uint32]
         lib.orc_adam_new.restype = C.c_void_p
         lib.orc_adam_new.argtypes = [C.c_float] * 5 + [C.c_int, C.c_int]
         lib.orc_adam_free.restype = None
@@ -196,15 +202,32 @@ class Oracle(_Codecs):
                                           per_rank, world, n, out_idx, out_val)
         return out_idx[:m], out_val[:m]
 
-    def sgd_new(self, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, maximize=False):
-        return self.lib.orc_sgd_new(lr, momentum, dampening, weight_decay, int(nesterov), int(maximize))
+    def sgd_new(self, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, maximize=False,
+                smart_momentum=False):
+        h = self.lib.orc_sgd_new(lr, momentum, dampening, weight_decay, int(nesterov), int(maximize))
+        self.lib.orc_sgd_smart(h, int(smart_momentum))
+        return h
+
+    def sgd_smart(self, h, on: bool):
+        """configure("smart_momentum", on) (sgd.cpp:291-292)."""
+        self.lib.orc_sgd_smart(h, int(on))
+
+    def sgd_iter(self, h) -> int:
+        return int(self.lib.orc_sgd_iter(h))
+
+    def sgd_last(self, h, name, n):
+        """The name's last-touched iterations, or None before its first call with momentum."""
+        out = np.zeros(n, np.uint32)
+        rc = self.lib.orc_sgd_last(h, name.encode(), out, n)
+        return None if rc else out
 
     def sgd_free(self, h):
         self.lib.orc_sgd_free(h)
 
     def sgd_apply(self, h, name, param, g, gidx):
-        self.lib.orc_sgd_apply(h, name.encode(), param, param.size, np.ascontiguousarray(g, np.float32),
-                               np.ascontiguousarray(gidx, np.uint32), len(g))
+        if self.lib.orc_sgd_apply(h, name.encode(), param, param.size, np.ascontiguousarray(g, np.float32),
+                                  np.ascontiguousarray(gidx, np.uint32), len(g)):
+            raise RuntimeError(self.lib.orc_last_error().decode())
 
     def sgd_momentum(self, h, name, n):
         out = np.zeros(n, np.float32)

@@ -5,7 +5,8 @@
  * (/root/reference/backend/src/optim/sgd.cpp, compiled in place by
  * oracle/Makefile into oracle/_ref/libstg_ref_sgd.so against the local torch
  * headers/libraries).  Drives SGD::configure (sgd.cpp:265-300) and
- * SGD::optimize_raw (sgd.cpp:34-263).
+ * SGD::optimize_raw (sgd.cpp:34-263); sets smart_momentum (sgd.cpp:291-292)
+ * and reads back the last-touched array and the iteration count.
  */
 #include <cstring>
 #include <memory>
@@ -44,5 +45,17 @@ REF_API int ref_sgd_momentum(void *o, const char *name, float *out, uint32_t len
     auto it = s->m_optim_state_b.find(name);
     if (it == s->m_optim_state_b.end()) return -1;
     std::memcpy(out, it->second.get(), sizeof(float) * len);
+    return 0;
+}
+REF_API void ref_sgd_smart(void *o, int on) {
+    std::string k = "smart_momentum";
+    static_cast<SGD *>(o)->configure(k, (bool)on);
+}
+REF_API uint32_t ref_sgd_iter(void *o) { return static_cast<SGD *>(o)->m_iter; }
+REF_API int ref_sgd_last(void *o, const char *name, uint32_t *out, uint32_t len) {
+    auto *s = static_cast<SGD *>(o);
+    auto it = s->m_optim_state_last.find(name);
+    if (it == s->m_optim_state_last.end()) return -1;
+    std::memcpy(out, it->second.get(), sizeof(uint32_t) * len);
     return 0;
 }

@@ -240,34 +240,50 @@ size_t tv_compress(Tv *h, uint64_t key, const float *src, size_t n, uint32_t k, 
 }
 
 // ---------------------------------------------------------------------------
-// Sparse SGD, scalar path (optim/sgd.cpp:34-55, 221-263), smart momentum off.
+// Sparse SGD, scalar path (optim/sgd.cpp:34-55, 221-263).
+// Smart momentum (sgd.cpp:54, 225-232, 258-259): a per-name array of the
+// iteration that last touched each element, allocated zeroed with the momentum
+// buffer (:46-47) whether or not the option is on.  Where the momentum stands,
+// the factor (float)pow((double)m, (double)(iter - last[idx])) stands -- the
+// ternary's type is double, stored in a float -- and m itself at iteration 0.
+// The reference asserts the factor in [0, 1); nothing is skipped here: an index
+// repeated in a call simply sees pow(m, 0) == 1 the second time.  With the
+// option on and momentum 0 the reference reads a null array; here the call is
+// refused (false, orc_last_error) and changes nothing.
 // ---------------------------------------------------------------------------
 struct Sgd {
     float lr = 1e-3f, momentum = 0.f, weight_decay = 0.f, dampening = 0.f;
-    bool nesterov = false, maximize = false;
+    bool nesterov = false, maximize = false, smart = false;
     uint32_t iter = 0;
     std::mutex mu;
     std::unordered_map<std::string, std::vector<float>> b;
+    std::unordered_map<std::string, std::vector<uint32_t>> last;
 };
 
-void sgd_apply(Sgd *o, const std::string &name, float *param, uint32_t param_len, const float *g_in,
+bool sgd_apply(Sgd *o, const std::string &name, float *param, uint32_t param_len, const float *g_in,
                const uint32_t *gidx, uint32_t glen) {
+    if (o->smart && o->momentum == 0.f) return false;  // no last-touched array exists
     bool first = false;
     float *pb = nullptr;
+    uint32_t *pl = nullptr;
     {
         std::lock_guard<std::mutex> g(o->mu);
         if (o->momentum != 0.f && o->b.find(name) == o->b.end()) {
             o->b[name].assign(param_len, 0.f);
+            o->last[name].assign(param_len, 0u);
             first = true;
         }
         if (o->momentum != 0.f) pb = o->b[name].data();
+        if (o->smart) pl = o->last[name].data();
     }
     const double lr = o->maximize ? -static_cast<double>(o->lr) : static_cast<double>(o->lr);
     for (uint32_t i = 0; i < glen; ++i) {
         const uint32_t id = gidx[i];
         const float x = param[id];
         float g = g_in[i];
-        const float m = o->momentum;
+        float m = o->momentum;
+        if (o->smart && o->iter != 0)
+            m = static_cast<float>(std::pow(static_cast<double>(o->momentum), static_cast<double>(o->iter - pl[id])));
         if (o->weight_decay != 0.f) g = std::fmaf(o->weight_decay, x, g);
         if (o->momentum != 0.f) {
             float bnew;
@@ -278,8 +294,10 @@ void sgd_apply(Sgd *o, const std::string &name, float *param, uint32_t param_len
             pb[id] = bnew;
         }
         param[id] = static_cast<float>(std::fma(-lr, static_cast<double>(g), static_cast<double>(x)));
+        if (o->smart) pl[id] = o->iter;
     }
     o->iter++;
+    return true;
 }
 
 // ---------------------------------------------------------------------------
@@ -569,9 +587,21 @@ ORC_API void *orc_sgd_new(float lr, float momentum, float dampening, float weigh
     return o;
 }
 ORC_API void orc_sgd_free(void *o) { delete static_cast<Sgd *>(o); }
-ORC_API void orc_sgd_apply(void *o, const char *name, float *param, uint32_t param_len, const float *g,
-                           const uint32_t *gidx, uint32_t glen) {
-    sgd_apply(static_cast<Sgd *>(o), name, param, param_len, g, gidx, glen);
+ORC_API int orc_sgd_apply(void *o, const char *name, float *param, uint32_t param_len, const float *g,
+                          const uint32_t *gidx, uint32_t glen) {
+    if (sgd_apply(static_cast<Sgd *>(o), name, param, param_len, g, gidx, glen)) return 0;
+    g_err = "smart_momentum needs momentum != 0";
+    return -1;
+}
+ORC_API void orc_sgd_smart(void *o, int on) { static_cast<Sgd *>(o)->smart = on != 0; }
+ORC_API uint32_t orc_sgd_iter(void *o) { return static_cast<Sgd *>(o)->iter; }
+ORC_API int orc_sgd_last(void *o, const char *name, uint32_t *out, uint32_t len) {
+    auto *p = static_cast<Sgd *>(o);
+    std::lock_guard<std::mutex> g(p->mu);
+    auto it = p->last.find(name);
+    if (it == p->last.end()) return -1;
+    std::memcpy(out, it->second.data(), sizeof(uint32_t) * std::min<size_t>(len, it->second.size()));
+    return 0;
 }
 ORC_API int orc_sgd_momentum(void *o, const char *name, float *out, uint32_t len) {
     auto *p = static_cast<Sgd *>(o);

@@ -13,6 +13,28 @@ def fbits(x) -> int:
     return int(np.float32(x).view(np.uint32))
 
 
+QNAN = np.uint32(0x7FC00000)
+
+
+def canon_nan(a: np.ndarray) -> np.ndarray:
+    """The bit patterns of a float32 array with every NaN mapped to 0x7fc00000."""
+    a = np.ascontiguousarray(a, np.float32)
+    return np.where(np.isnan(a), QNAN, a.view(np.uint32)).astype(np.uint32)
+
+
+def assert_same_f32(got, exp, what: str = ""):
+    """Where `exp` is NaN, `got` must be NaN (any sign and payload: x86 and the
+    GPU pick different ones for inf - inf and 0 / 0, which is no property of the
+    code under test); everywhere else the bit patterns are equal."""
+    got, exp = np.ascontiguousarray(got, np.float32).ravel(), np.ascontiguousarray(exp, np.float32).ravel()
+    assert got.shape == exp.shape, f"{what}: shape {got.shape} vs {exp.shape}"
+    bad = np.flatnonzero(canon_nan(got) != canon_nan(exp))
+    if bad.size:
+        f = int(bad[0])
+        raise AssertionError(f"{what}: {bad.size} of {exp.size} elements differ, first at {f}: got "
+                             f"{got[f]!r} (0x{int(bits(got)[f]):08x}), expected {exp[f]!r} (0x{int(bits(exp)[f]):08x})")
+
+
 def assert_same_pairs(idx_a, val_a, idx_b, val_b, n: int):
     """Bit-exact equality of the first n (idx, val) pairs as sets (order-free)."""
     ia, ib = np.asarray(idx_a[:n], np.uint32), np.asarray(idx_b[:n], np.uint32)

@@ -149,8 +149,7 @@ class _Run:
         self.a, self.b = cls(**opts), cls(**opts)
         self.h = None
         if with_oracle:
-            o = {k: v for k, v in opts.items() if k != "smart_momentum"}
-            self.h = oracle.sgd_new(**o) if kind == "sgd" else oracle.adam_new(**o)
+            self.h = oracle.sgd_new(**opts) if kind == "sgd" else oracle.adam_new(**opts)
         self.momentum = bool(opts.get("momentum"))
         self.params = {}  # name -> (pa, pb, po)
 
@@ -283,7 +282,7 @@ def test_full_launch_groups(gpu, oracle, scratch, T, kind):
 ITER_OPTS = {
     "sgd_momentum": ("sgd", dict(lr=0.05, momentum=0.9), True),
     "sgd_nesterov_wd": ("sgd", dict(lr=0.05, momentum=0.9, nesterov=True, weight_decay=0.01), True),
-    "sgd_smart": ("sgd", dict(lr=0.05, momentum=0.9, dampening=0.1, smart_momentum=True), False),
+    "sgd_smart": ("sgd", dict(lr=0.05, momentum=0.9, dampening=0.1, smart_momentum=True), True),
     "adam": ("adam", dict(lr=0.01, weight_decay=0.01), True),
     "adam_amsgrad": ("adam", dict(lr=0.01, weight_decay=0.01, amsgrad=True), False),  # its running max follows the stream order
 }

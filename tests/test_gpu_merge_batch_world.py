@@ -118,7 +118,7 @@ class _WRun(_Run):
 OPTS = {
     "sgd_momentum": ("sgd", dict(lr=0.05, momentum=0.9), True),
     "sgd_smart_nesterov_wd": ("sgd", dict(lr=0.05, momentum=0.9, nesterov=True, weight_decay=0.01,
-                                          smart_momentum=True), False),
+                                          smart_momentum=True), True),
     "adam_wd": ("adam", dict(lr=0.01, weight_decay=0.01), True),
     "adam_amsgrad": ("adam", dict(lr=0.01, weight_decay=0.01, amsgrad=True), False),
 }
