@@ -526,6 +526,74 @@ int stg_merge_optimize_adam_batch_device(stg_adam_t o, const stg_merge_task_t *t
  * STG_ERR_INVALID for a null `out`, before any device call. */
 int stg_merge_batch_launches(void *stream, uint64_t *out);
 
+/* Element types of a model replica (stg_replica_t.dtype). */
+#define STG_DT_F32  0
+#define STG_DT_BF16 1
+#define STG_DT_F16  2
+
+/* One model copy that receives a task's changed parameters: param_len elements
+ * of `dtype` at d_param, aligned to the element size (no more is needed). */
+typedef struct stg_replica {
+    void *d_param;
+    int dtype;                     /* STG_DT_*                                                 */
+} stg_replica_t;                   /* 16 bytes on LP64: d_param at 0, dtype at 8               */
+
+/* One parameter tensor of a publish call: the master copy a step has just
+ * written, the step's merged stream (d_out_idx / d_out_count of
+ * stg_merge_optimize_*), and the replicas to bring up to date. */
+typedef struct stg_publish_task {
+    const float *d_param;          /* the master parameter, param_len floats, read only        */
+    uint32_t param_len;
+    const uint32_t *d_idx;         /* the step's merged indices (its d_out_idx)                */
+    const uint32_t *d_count;       /* device word: pairs in d_idx (its d_out_count)            */
+    uint32_t idx_cap;              /* slots d_idx holds (per_rank * world): the grid's bound   */
+    const stg_replica_t *replicas; /* host array, read at call time                            */
+    int nreplicas;                 /* 1..16                                                    */
+} stg_publish_task_t;              /* 56 bytes on LP64: d_param at 0, param_len at 8, d_idx at 16,
+                                      d_count at 24, idx_cap at 32, replicas at 40, nreplicas at 48 */
+
+/* Publishes a step's changed parameters to the node's model replicas: the
+ * device form of ModuleH2DCopy::run (engine/modules/h2d_copy.cpp:31-56,
+ * gpu_param_tensor.copy_(cpu_param_tensor) per GPU), for parameters that live
+ * on the node master's GPU.  The sparse steps write a parameter only at the
+ * indices of the merged stream (sgd.cpp:221-260, adam.cpp:19-86), so a replica
+ * that equalled the parameter before the step equals it again after k element
+ * stores instead of a dense copy of param_len.
+ *   Per task, with c = *d_count read on the device: for every i < c with
+ * j = d_idx[i] < param_len, and every replica r, replica_r[j] = cvt_r(d_param[j]).
+ * cvt is the identity for STG_DT_F32 and round-to-nearest-even for
+ * STG_DT_BF16 / STG_DT_F16 (overflow to inf, fp16 subnormals kept, a NaN stays
+ * a NaN of unspecified payload).  Nothing else is written: an element whose
+ * index is not among the first c slots is never stored to, not even with its
+ * old value (peers may be reading their replica); slots c .. idx_cap-1 are
+ * ignored; an index >= param_len is skipped, as the merge drops it; a
+ * repeated index writes the same value twice.  c > idx_cap -- 0xffffffff, the
+ * count a failed merge leaves, included -- publishes nothing for that task
+ * (that failure is sticky in stg_scatter_merge_check).  idx_cap == 0 or
+ * ntasks == 0 is STG_OK and launches nothing for it.
+ *   Asynchronous on `stream` of the current device and ordered after the step
+ * enqueued on it before.  A replica may be a peer GPU's memory when P2P access
+ * is enabled (as the sources of stg_gather_add_device); the stores are
+ * complete when the work on `stream` is, and making a peer's stream wait for
+ * them (an event recorded on `stream`) is the caller's job.  Peer (xGMI)
+ * replicas have not been run on hardware; tests and timings use replicas on
+ * the master's GPU.
+ *   Up to 16 tasks share one launch, workgroups of 1024 stream slots dealt to
+ * the tasks in order; a launch also closes before its grid would pass 8
+ * workgroups per compute unit (the bound of the send path's gather), and a
+ * task larger than that runs in a launch of its own.  The grid is sized from
+ * idx_cap; workgroups past c leave after reading the count.
+ *   All or nothing: every task is checked before any device call, and a
+ * refused call (STG_ERR_INVALID) names the task index in stg_last_error():
+ * null `tasks` with ntasks > 0; nreplicas outside 1..16; an unknown dtype;
+ * with idx_cap > 0 a null d_param, d_idx, d_count, replicas or replica
+ * pointer, or param_len == 0; a replica pointer not aligned to its element. */
+int stg_param_publish_batch_device(const stg_publish_task_t *tasks, size_t ntasks, void *stream);
+/* Diagnostics, plain host arithmetic (no device): the launches a publish call
+ * with these idx_cap values makes on a device of num_cu compute units (0 for
+ * a null array with ntasks > 0 or num_cu < 1). */
+int stg_debug_publish_launches(const uint32_t *idx_caps, size_t ntasks, int num_cu);
+
 /* Synthetic fp32 buckets from the integer-only generator of SURVEY 8(d)
  * (dist 0 = D1, 1 = D2 heavy tail, 2 = D3 zeros with prob param/1e4);
  * bit-identical to oracle/stg_oracle.cpp:orc_synth_fill. */

@@ -60,6 +60,19 @@ class StgSendTask(C.Structure):
                 ("num_gpus", C.c_int), ("wire_flag", C.c_int)]
 
 
+class StgReplica(C.Structure):
+    """``stg_replica_t``: one model copy a publish task writes (dtype: ``STG_DT_*``)."""
+    _fields_ = [("d_param", C.c_void_p), ("dtype", C.c_int)]
+
+
+class StgPublishTask(C.Structure):
+    """``stg_publish_task_t``: one parameter tensor of ``stg_param_publish_batch_device``."""
+    _fields_ = [("d_param", C.c_void_p), ("param_len", C.c_uint32), ("d_idx", C.c_void_p), ("d_count", C.c_void_p),
+                ("idx_cap", C.c_uint32), ("replicas", C.POINTER(StgReplica)), ("nreplicas", C.c_int)]
+
+
+STG_DT_F32, STG_DT_BF16, STG_DT_F16 = 0, 1, 2
+
 _lib: C.CDLL | None = None
 
 _SIGS = {
@@ -133,6 +146,8 @@ _SIGS = {
     "stg_merge_optimize_sgd_batch_device": (C.c_int, [C.c_void_p, C.POINTER(StgMergeTask), C.c_size_t, C.c_void_p]),
     "stg_merge_optimize_adam_batch_device": (C.c_int, [C.c_void_p, C.POINTER(StgMergeTask), C.c_size_t, C.c_void_p]),
     "stg_merge_batch_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "stg_param_publish_batch_device": (C.c_int, [C.POINTER(StgPublishTask), C.c_size_t, C.c_void_p]),
+    "stg_debug_publish_launches": (C.c_int, [C.POINTER(C.c_uint32), C.c_size_t, C.c_int]),
     "stg_synth_fill_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_int, C.c_uint32, C.c_void_p]),
     "stg_last_error": (C.c_char_p, []),
 }

@@ -708,6 +708,26 @@ auto stream_packer(uint64_t limit, hipError_t (*launch)(const Table &, uint32_t,
 }
 constexpr uint64_t GRID_MAX = 0x7fffffffull;  // workgroups of one launch
 
+// The launches of a publish call (publish.hip), by the one rule the entry
+// point and stg_debug_publish_launches share: task i of cap(i) > 0 index slots
+// takes ceil(cap / PUBLISH_TILE) workgroups of a table that closes at
+// PUBLISH_BATCH tasks or before num_cu * PUBLISH_GRID_PER_CU workgroups;
+// fill(i, item) writes the item, launch(table, workgroups) enqueues it.
+template <class Cap, class Fill, class Launch>
+int publish_pack(size_t ntasks, int num_cu, Cap cap, Fill fill, Launch launch) {
+    auto pk = stg::make_packer<stg::PublishBatch>((uint64_t)num_cu * stg::PUBLISH_GRID_PER_CU, launch);
+    for (size_t i = 0; i < ntasks; ++i) {
+        const uint32_t c = cap(i);
+        if (!c) continue;
+        stg::PublishTask *d;
+        if (const int rc = pk.add(((uint64_t)c + stg::PUBLISH_TILE - 1) / stg::PUBLISH_TILE, &d)) return rc;
+        fill(i, d);
+    }
+    return pk.flush();
+}
+// low address bits that must be clear for a replica of this STG_DT_* type
+uintptr_t publish_elem_mask(int dtype) { return dtype == STG_DT_F32 ? 3u : 1u; }
+
 }  // namespace
 
 extern "C" {
@@ -2098,6 +2118,67 @@ int stg_wire_decode_batch_device(const stg_wire_rx_t *streams, size_t nstreams, 
         d->flag = (uint32_t)w.flag;
     }
     return b.flush();
+}
+
+int stg_param_publish_batch_device(const stg_publish_task_t *tasks, size_t ntasks, void *stream) {
+    if (ntasks && !tasks) return fail(STG_ERR_INVALID, "null task array");
+    bool any = false;
+    for (size_t i = 0; i < ntasks; ++i) {
+        const stg_publish_task_t &t = tasks[i];
+        auto bad = [&](const std::string &what) {
+            return fail(STG_ERR_INVALID, "publish task " + std::to_string(i) + ": " + what);
+        };
+        if (t.nreplicas < 1 || t.nreplicas > (int)stg::PUBLISH_MAXR) return bad("nreplicas outside 1..16");
+        if (t.idx_cap) {
+            if (!t.d_param || !t.d_idx || !t.d_count || !t.replicas) return bad("null argument");
+            if (!t.param_len) return bad("empty parameter");
+            any = true;
+        }
+        for (int r = 0; t.replicas && r < t.nreplicas; ++r) {
+            const stg_replica_t &p = t.replicas[r];
+            if (p.dtype != STG_DT_F32 && p.dtype != STG_DT_BF16 && p.dtype != STG_DT_F16)
+                return bad("replica " + std::to_string(r) + ": unknown dtype");
+            if (t.idx_cap && !p.d_param) return bad("replica " + std::to_string(r) + ": null pointer");
+            if (reinterpret_cast<uintptr_t>(p.d_param) & publish_elem_mask(p.dtype))
+                return bad("replica " + std::to_string(r) + ": pointer not aligned to its element size");
+        }
+    }
+    if (!any) return STG_OK;
+    int ncu;
+    if (const int rc = device_cus(&ncu)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool runs = env_int(getenv("STG_DEBUG_PUBLISH_SCALAR"), 0) != 1;  // measurements: the scalar-only kernel
+    return publish_pack(
+        ntasks, ncu, [&](size_t i) { return tasks[i].idx_cap; },
+        [&](size_t i, stg::PublishTask *d) {
+            const stg_publish_task_t &t = tasks[i];
+            d->param = t.d_param;
+            d->idx = t.d_idx;
+            d->count = t.d_count;
+            d->n = t.param_len;
+            d->cap = t.idx_cap;
+            d->nrep = (uint32_t)t.nreplicas;
+            for (int r = 0; r < t.nreplicas; ++r) {
+                d->rep[r] = t.replicas[r].d_param;
+                d->dtypes |= (uint32_t)t.replicas[r].dtype << (2 * r);
+            }
+        },
+        [&](stg::PublishBatch &w, uint32_t blocks) -> int {
+            HIP_TRY(stg::launch_param_publish_batch(w, blocks, runs, s));
+            return STG_OK;
+        });
+}
+
+int stg_debug_publish_launches(const uint32_t *idx_caps, size_t ntasks, int num_cu) {
+    if ((ntasks && !idx_caps) || num_cu < 1) return 0;
+    int launches = 0;
+    publish_pack(
+        ntasks, num_cu, [&](size_t i) { return idx_caps[i]; }, [](size_t, stg::PublishTask *) {},
+        [&](stg::PublishBatch &, uint32_t) -> int {
+            ++launches;
+            return STG_OK;
+        });
+    return launches;
 }
 
 int stg_synth_fill_device(float *d_dst, size_t n, uint64_t seed, int dist, uint32_t param, void *stream) {

@@ -594,6 +594,37 @@ struct SendFinishBatch {
 };
 static_assert(sizeof(SendFinishBatch) <= 2048, "kernel arguments: stay well under 4 KiB");
 hipError_t launch_ef_pack_batch(const SendFinishBatch &w, uint32_t blocks, hipStream_t s);
+// Publishing a step's changed parameters to the node's model replicas
+// (publish.hip): replica[j] = cvt(param[j]) at the indices of the step's
+// merged stream, for up to PUBLISH_BATCH tasks per launch.  The table --
+// replica pointers included, as SendGather's source pointers -- travels by
+// value in the kernel arguments, workgroups dealt by blk0 as above.
+constexpr uint32_t PUBLISH_BATCH = 16;    // tasks per launch
+constexpr uint32_t PUBLISH_MAXR = 16;     // replicas per task
+constexpr uint32_t PUBLISH_WP = 4;        // consecutive stream slots per lane, as MERGE_BATCH_WP
+constexpr uint32_t PUBLISH_TILE = 1024;   // stream slots per workgroup
+static_assert(PUBLISH_TILE == PUBLISH_WP * STG_WG, "one lane, PUBLISH_WP slots");
+constexpr uint32_t PUBLISH_GRID_PER_CU = 8;  // a launch closes before num_cu * 8 workgroups, as the send path's gather
+constexpr uint32_t PUBLISH_F32 = 0, PUBLISH_BF16 = 1, PUBLISH_F16 = 2;  // = STG_DT_*
+struct PublishTask {
+    const float *param;            // the master parameter, n floats (read only)
+    const uint32_t *idx;           // the step's merged indices ...
+    const uint32_t *count;         // ... and the device word that counts them
+    void *rep[PUBLISH_MAXR];       // rep[0 .. nrep-1], element-aligned
+    uint32_t dtypes;               // rep[r]'s type in bits 2 r, 2 r + 1 (one scalar word, not a table to load from)
+    uint32_t n;
+    uint32_t cap;                  // slots at idx: a count above it publishes nothing
+    uint32_t nrep;
+    uint32_t blk0;                 // first workgroup of this task in the launch
+};
+struct PublishBatch {
+    PublishTask t[PUBLISH_BATCH];
+    uint32_t nt;
+};
+static_assert(sizeof(PublishBatch) <= 3072, "kernel arguments: stay under 4 KiB");
+// runs: consecutive indices take wide stores where the replica's address
+// allows (false: every element a store of its own; kept for measurements)
+hipError_t launch_param_publish_batch(const PublishBatch &w, uint32_t blocks, bool runs, hipStream_t s);
 struct WireRx {  // one received stream of a batched decode
     const void *idx_in, *val_in;
     uint32_t *idx;

@@ -20,11 +20,12 @@ import ctypes as C
 
 import numpy as np
 
-from ._capi import CodecError, StgMergeTask, StgRankStream, StgWireRx, check, lib
+from ._capi import (STG_DT_BF16, STG_DT_F16, STG_DT_F32, CodecError, StgMergeTask, StgPublishTask, StgRankStream,
+                    StgReplica, StgWireRx, check, lib)
 from .compressor import Compressor, make_compressor
 
 __all__ = ["CodecEngine", "SparseSGD", "MergeTasks", "merge_numel", "api_numel", "scatter_merge", "scatter_merge_wire",
-           "wire_decode_batch", "owner_of", "merge_batch_launches"]
+           "wire_decode_batch", "owner_of", "merge_batch_launches", "PublishTasks", "publish_params"]
 
 
 def merge_numel(n: int, ratio: float, world: int = 1) -> int:
@@ -467,6 +468,11 @@ class MergeTasks:
             self._keep.append((ranks, nm, param, streams, dense, mark))
             self.outputs.append((out_idx, out_val, count))
 
+    @property
+    def params(self):
+        """The items' parameter tensors, in order."""
+        return [k[2] for k in self._keep]
+
 
 def _merge_optimize_batch(fn, h, items):
     """The iteration's ModuleCpuOptimize tasks through one C call (``fn``):
@@ -479,6 +485,90 @@ def _merge_optimize_batch(fn, h, items):
     if rc:
         check(rc)
     return tasks.outputs
+
+
+class PublishTasks:
+    """A prebuilt ``stg_publish_task_t`` array for ``publish_params``,
+    marshalled and validated once (a model's parameters, merged-stream buffers
+    and replicas do not move between iterations).  Each item is ``(param,
+    out_idx, count, replicas)``: the float32 master parameter, the step's
+    merged indices and device count (``merge_optimize_batch``'s ``out_idx`` and
+    ``count``; ``idx_cap = out_idx.numel()``), and 1..16 contiguous replica
+    tensors of ``param.numel()`` elements, float32, bfloat16 or float16, each
+    on any HIP device the master can reach.  The array keeps every tensor it
+    points at alive."""
+
+    def __init__(self, items):
+        import torch
+        dts = {torch.float32: STG_DT_F32, torch.bfloat16: STG_DT_BF16, torch.float16: STG_DT_F16}
+        items = list(items)
+        self.count = len(items)
+        self.array = (StgPublishTask * max(self.count, 1))()
+        self.device = items[0][0].device if items else None
+        self._keep = []
+        for j, it in enumerate(items):
+            if len(it) != 4:
+                raise ValueError(f"publish_params: item {j}: (param, out_idx, count, replicas) expected")
+            param, out_idx, count, replicas = it
+            replicas = list(replicas)
+            if param.dtype != torch.float32 or not param.is_contiguous():
+                raise ValueError(f"publish_params: item {j}: the parameter must be contiguous float32")
+            if out_idx.dtype != torch.int32 or not out_idx.is_contiguous() or count.dtype != torch.int32 \
+                    or count.numel() < 1:
+                raise ValueError(f"publish_params: item {j}: out_idx must be contiguous int32 and count an int32 word")
+            if not 1 <= len(replicas) <= 16:
+                raise ValueError(f"publish_params: item {j}: replicas outside 1..16")
+            reps = (StgReplica * len(replicas))()
+            for r, t in enumerate(replicas):
+                if t.dtype not in dts:
+                    raise ValueError(f"publish_params: item {j}: replica {r}: dtype {t.dtype} is not float32, "
+                                     "bfloat16 or float16")
+                if t.numel() != param.numel():
+                    raise ValueError(f"publish_params: item {j}: replica {r}: size {t.numel()} is not the "
+                                     f"parameter's {param.numel()}")
+                if not t.is_contiguous():
+                    raise ValueError(f"publish_params: item {j}: replica {r}: not contiguous")
+            if not all(t.is_cuda for t in [param, out_idx, count] + replicas):
+                raise ValueError(f"publish_params: item {j}: tensors must be on a HIP device")
+            if param.device != self.device or out_idx.device != self.device or count.device != self.device:
+                raise ValueError(f"publish_params: item {j}: parameter, out_idx and count must be on the master's "
+                                 "device")
+            for r, t in enumerate(replicas):
+                reps[r] = StgReplica(t.data_ptr(), dts[t.dtype])
+            self.array[j] = StgPublishTask(param.data_ptr(), param.numel(), out_idx.data_ptr(), count.data_ptr(),
+                                           out_idx.numel(), reps, len(replicas))
+            self._keep.append((reps, param, out_idx, count, replicas))
+
+    @classmethod
+    def from_merge(cls, merge_tasks: MergeTasks, replicas_per_item):
+        """The publish tasks of a ``MergeTasks`` array: item j's parameter and
+        its ``outputs[j]`` (merged indices and count), with
+        ``replicas_per_item[j]`` as its replicas."""
+        replicas_per_item = list(replicas_per_item)
+        if len(replicas_per_item) != merge_tasks.count:
+            raise ValueError("publish_params: one replica list per merge task expected")
+        return cls([(p, o[0], o[2], reps) for p, o, reps in zip(merge_tasks.params, merge_tasks.outputs,
+                                                                replicas_per_item)])
+
+
+def publish_params(items) -> None:
+    """ModuleH2DCopy::run (h2d_copy.cpp:31-56) for device-resident parameters,
+    through ``stg_param_publish_batch_device``: every replica of every item
+    receives the parameter's value at the indices the step just wrote (the
+    first ``count`` of ``out_idx``; bfloat16 / float16 replicas rounded to
+    nearest even) and is otherwise left alone.  Runs on the current stream of
+    the master's device, after the step enqueued there; a peer's stream must
+    be made to wait on it by the caller.  ``items`` as ``PublishTasks`` takes
+    them, or a prebuilt ``PublishTasks`` (no per-call marshalling)."""
+    import torch
+    tasks = items if isinstance(items, PublishTasks) else PublishTasks(items)
+    if not tasks.count:
+        return
+    with torch.cuda.device(tasks.device):
+        rc = lib().stg_param_publish_batch_device(
+            tasks.array, tasks.count, C.c_void_p(torch.cuda.current_stream(tasks.device.index).cuda_stream))
+    if rc:
+        check(rc)
 
 
 class SparseSGD:
