@@ -71,12 +71,19 @@ int stg_codec_compress_host(stg_codec_t h, const char *key, const float *src, si
 /* Same contract on device-resident buffers, fully asynchronous on `stream`:
  * no host synchronisation, per-key threshold state stays on the device.
  * The returned pair count is written to *d_count (device uint32).  dst
- * buffers are caller-owned with capacity idx_cap (val_cap >= idx_cap). */
+ * buffers are caller-owned with capacity idx_cap (val_cap >= idx_cap).
+ * d_src, d_idx and d_val need only the alignment of their element (4 bytes;
+ * 2 bytes for a 16-bit wire-form output): any such address gives the same
+ * results and nothing outside [d_idx, d_idx + idx_cap), [d_val, d_val +
+ * idx_cap) is written.  16-byte alignment of all three selects the vector
+ * emission (the fast path); top-k reads a 16-byte aligned d_src by float4. */
 int stg_codec_compress_device(stg_codec_t h, const char *key, const float *d_src, size_t n, uint32_t k,
                               uint32_t *d_idx, size_t idx_cap, float *d_val, size_t val_cap,
                               int32_t idx_offset, uint32_t *d_count, void *stream);
 
-/* One bucket of a batched call: the arguments of one compress_device call. */
+/* One bucket of a batched call: the arguments of one compress_device call
+ * (d_src, d_idx, d_val: element-aligned is enough, as there; 16-byte
+ * alignment of all three selects the bucket's vector emission). */
 typedef struct stg_bucket {
     const char *key;
     const float *d_src;
