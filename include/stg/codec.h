@@ -375,7 +375,12 @@ int stg_gather_add_device(float *d_grad0, const float *d_residual, const float *
  * encode writes numel indices as uint16 (flag & 1) or uint32 and numel values
  * as fp16 bits (flag & 2) or float; decode is the receiver's inverse
  * (comm_manager.cpp:877-906).  Both reproduce the reference's bytes exactly,
- * including its SIMD-block / scalar-tail differences (wire.hip).  Async. */
+ * including its SIMD-block / scalar-tail differences (wire.hip).  NaNs cross
+ * quiet in both directions, as the x86 conversions leave them: a float32 NaN
+ * is sent as sign | 0x7e00 | payload >> 13; a received fp16 NaN, signalling
+ * or quiet, becomes the float32 NaN sign | 0x7fc00000 | payload << 13 (0x7c01
+ * -> 0x7fc02000).  The same holds wherever a 16-bit stream is read in place
+ * (the MERGE calls below).  Async. */
 #define STG_WIRE_U16_IDX 0x01
 #define STG_WIRE_F16_VAL 0x02
 int stg_wire_flag(uint64_t tensor_numel, int fp16_values);

@@ -2,6 +2,9 @@
 
 * ``Oracle``    wraps ``oracle/liboracle.so`` (clean-room restatement,
                 oracle/stg_oracle.cpp); travels to the GPU box.
+* ``IsaWire``   wraps ``oracle/libisa_wire.so`` (the x86 operations of the wire
+                casts, oracle/isa_wire.cpp); the yardstick of the 16-bit wire
+                forms; travels to the GPU box.
 * ``Reference`` wraps ``oracle/_ref/libstg_ref.so`` (the reference's own
                 backend/src/compress sources compiled in place; this container only).
 
@@ -18,11 +21,13 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ORACLE_SO = os.path.join(HERE, "liboracle.so")
+ISA_SO = os.path.join(HERE, "libisa_wire.so")
 REF_SO = os.path.join(HERE, "_ref", "libstg_ref.so")
 REF_SRC = "/root/reference/backend/src"
 
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
+_u16p = np.ctypeslib.ndpointer(np.uint16, flags="C_CONTIGUOUS")
 
 
 def build(ref: bool | None = None) -> None:
@@ -280,6 +285,92 @@ class Oracle(_Codecs):
         m, v, vmax = np.zeros(n, np.float32), np.zeros(n, np.float32), C.c_float()
         tick = self.lib.orc_adam_state(h, name.encode(), m, v, n, C.byref(vmax))
         return None if tick < 0 else (m, v, np.float32(vmax.value), tick)
+
+
+class IsaWire:
+    """The wire casts as the x86 operations themselves (oracle/isa_wire.cpp: one
+    function per operation, executed by this CPU).  The block / tail rule of
+    comm_manager.cpp:486-590 is composed here: positions below
+    8 * ((m - 1) // 8) take the block operation, the rest the tail's.  Shares
+    no conversion code with ``Oracle.wire_encode`` / ``wire_decode``."""
+
+    def __init__(self, path: str = ISA_SO):
+        lib = _load(path)
+        self.lib = lib
+        for name, src, dst in (("isa_cvtps_ph", _f32p, _u16p), ("isa_cvtph_ps", _u16p, _f32p),
+                               ("isa_packs_epi32", _u32p, _u16p), ("isa_cvtepi16_epi32", _u16p, _u32p),
+                               ("isa_cvttss_si32_lo16", _f32p, _u16p), ("isa_u16_to_f32", _u16p, _f32p)):
+            f = getattr(lib, name)
+            f.restype = None
+            f.argtypes = [src, dst, C.c_size_t]
+
+    def _apply(self, name: str, src: np.ndarray, out_dtype, pad8: bool) -> np.ndarray:
+        n = src.size
+        m = (n + 7) // 8 * 8 if pad8 else n
+        a = np.zeros(m, src.dtype)
+        a[:n] = src
+        out = np.zeros(m, out_dtype)
+        getattr(self.lib, name)(a, out, m)
+        return out[:n]
+
+    # -- one operation over a whole array (any length: padded to 8 lanes) -----
+    def cvtps_ph(self, val) -> np.ndarray:
+        """_mm256_cvtps_ph(v, 0): float32 -> binary16 words, round to nearest even."""
+        return self._apply("isa_cvtps_ph", np.ascontiguousarray(val, np.float32), np.uint16, True)
+
+    def cvtph_ps(self, words) -> np.ndarray:
+        """_mm256_cvtph_ps: binary16 words -> float32."""
+        return self._apply("isa_cvtph_ps", np.ascontiguousarray(words, np.uint16), np.float32, True)
+
+    def packs_epi32(self, idx) -> np.ndarray:
+        """_mm_packs_epi32: int32 -> int16, signed saturation."""
+        return self._apply("isa_packs_epi32", np.ascontiguousarray(idx, np.uint32), np.uint16, True)
+
+    def cvtepi16_epi32(self, words) -> np.ndarray:
+        """_mm256_cvtepi16_epi32: int16 -> int32, sign extension."""
+        return self._apply("isa_cvtepi16_epi32", np.ascontiguousarray(words, np.uint16), np.uint32, True)
+
+    def cvttss_lo16(self, val) -> np.ndarray:
+        """(uint16_t)_mm_cvttss_si32: truncation to int32, the low 16 bits kept."""
+        return self._apply("isa_cvttss_si32_lo16", np.ascontiguousarray(val, np.float32), np.uint16, False)
+
+    def u16_to_f32(self, words) -> np.ndarray:
+        """(float) of a uint16_t."""
+        return self._apply("isa_u16_to_f32", np.ascontiguousarray(words, np.uint16), np.float32, False)
+
+    # -- the wire form ----------------------------------------------------------
+    @staticmethod
+    def simd_end(m: int) -> int:
+        return 8 * ((m - 1) // 8) if m else 0
+
+    def encode(self, idx, val, flag):
+        """(idx as u16 / u32 array, val as u16 / f32 array) of queueTx's casts."""
+        idx = np.ascontiguousarray(idx, np.uint32)
+        val = np.ascontiguousarray(val, np.float32)
+        se = self.simd_end(idx.size)
+        if flag & 1:
+            wi = np.concatenate([self.packs_epi32(idx[:se]), idx[se:].astype(np.uint16)])
+        else:
+            wi = idx.copy()
+        if flag & 2:
+            wv = np.concatenate([self.cvtps_ph(val[:se]), self.cvttss_lo16(val[se:])])
+        else:
+            wv = val.copy()
+        return wi, wv
+
+    def decode(self, widx, wval, flag):
+        """(u32 idx, f32 val) of the receiver's casts."""
+        widx, wval = np.ascontiguousarray(widx), np.ascontiguousarray(wval)
+        se = self.simd_end(widx.size)
+        if flag & 1:
+            idx = np.concatenate([self.cvtepi16_epi32(widx[:se]), widx[se:].astype(np.uint32)])
+        else:
+            idx = widx.astype(np.uint32)
+        if flag & 2:
+            val = np.concatenate([self.cvtph_ps(wval[:se]), self.u16_to_f32(wval[se:])])
+        else:
+            val = wval.view(np.float32).copy()
+        return idx, val
 
 
 class Reference(_Codecs):

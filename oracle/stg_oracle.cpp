@@ -384,8 +384,11 @@ void adam_apply(Adam *o, const std::string &name, float *param, uint32_t param_l
 //            to nearest even; tail `dst[i] = src[i]` with fp16_t = uint16_t
 //            (comm_manager.h:27), i.e. GCC's vcvttss2si to int32 (truncation,
 //            out of range / NaN -> 0x80000000) stored as the low 16 bits.
-//   f16->f32 (:550-567): blocks _mm256_cvtph_ps (exact); tail the integer
-//            value of the uint16 converted to float.
+//   f16->f32 (:550-567): blocks _mm256_cvtph_ps (exact; a signalling NaN
+//            comes out quiet, payload kept); tail the integer value of the
+//            uint16 converted to float.
+// tests/test_wire_isa_host.py pins all of this to the instructions themselves
+// (oracle/isa_wire.cpp) on every binary16 word and rounding boundary.
 // ---------------------------------------------------------------------------
 size_t wire_simd_end(size_t len) { return len ? 8 * ((len - 1) / 8) : 0; }
 
@@ -416,7 +419,7 @@ uint16_t f32_to_f16_rne(float f) {
 float f16_to_f32(uint16_t h) {
     const uint32_t sign = static_cast<uint32_t>(h & 0x8000u) << 16;
     uint32_t ex = (h >> 10) & 0x1fu, man = h & 0x3ffu, u;
-    if (ex == 0x1fu) u = sign | 0x7f800000u | (man << 13);
+    if (ex == 0x1fu) u = sign | 0x7f800000u | (man ? 0x00400000u | (man << 13) : 0u);  // a NaN widens quiet
     else if (ex) u = sign | ((ex + 112u) << 23) | (man << 13);
     else if (!man) u = sign;
     else {

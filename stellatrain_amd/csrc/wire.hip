@@ -10,15 +10,20 @@
 //   u16->u32: blocks = sign extension (_mm256_cvtepi16_epi32), tail = zero ext.
 //   f32->f16: blocks = IEEE binary16 RNE (_mm256_cvtps_ph(v, 0)); tail =
 //             (uint16_t)(int32)trunc(x), fp16_t being uint16_t (comm_manager.h:27)
-//   f16->f32: blocks = exact widening; tail = (float) of the uint16 integer
+//   f16->f32: blocks = exact widening (_mm256_cvtph_ps: a signalling NaN comes
+//             out with its quiet bit set); tail = (float) of the uint16 integer
 // Both sides reproduce those bytes, so a stream packed here decodes on a
 // reference peer exactly as one packed by the reference, and vice versa.
 //
 // The per-element casts live in wire_dev.h, shared with the thresholdv16
 // emission that writes the wire form directly.  One element per lane,
 // grid-stride: the stream is k pairs (1.3 MB at 64 MiB, k = 1 %), so the launch is latency-bound; loads and stores are coalesced
-// 4-byte / 2-byte runs per wave.  The fp16 conversion is integer arithmetic so
-// NaN payloads and subnormals match the x86 instruction bit for bit.
+// 4-byte / 2-byte runs per wave.  The fp16 conversions are integer arithmetic,
+// equal to the x86 instructions bit for bit on every input, ties, subnormals and
+// NaNs included: a NaN keeps its sign and the payload bits the target holds
+// and comes out quiet in either direction (vcvtps2ph, vcvtph2ps).  The tests
+// compare both casts with the executed instructions over every binary16 word
+// and every float32 rounding boundary (tests/test_gpu_wire_exhaustive.py).
 #include <algorithm>
 
 #include "ws.h"

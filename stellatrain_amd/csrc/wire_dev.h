@@ -42,7 +42,8 @@ __device__ __forceinline__ uint32_t f16_to_f32(uint32_t h) {
     const uint32_t sign = (h & 0x8000u) << 16;
     const uint32_t ex = (h >> 10) & 0x1fu;
     uint32_t man = h & 0x3ffu;
-    if (ex == 0x1fu) return sign | 0x7f800000u | (man << 13);
+    // inf; a NaN widens quiet (vcvtph2ps sets the quiet bit of a signalling one, payload kept)
+    if (ex == 0x1fu) return sign | 0x7f800000u | (man ? 0x00400000u | (man << 13) : 0u);
     if (ex) return sign | ((ex + 112u) << 23) | (man << 13);
     if (!man) return sign;
     const uint32_t lz = __clz(man) - 21;  // leading zeros within the 11-bit field (man < 0x400)
@@ -70,7 +71,7 @@ __device__ __forceinline__ uint32_t wire_val16(float f, size_t i, size_t wend) {
 __device__ __forceinline__ uint32_t wire_idx32(uint32_t w, size_t i, size_t wend) {
     return i < wend ? (uint32_t)(int32_t)(int16_t)w : w;
 }
-// blocks widen the fp16 exactly, the tail is (float) of the 16-bit integer
+// blocks widen the fp16 exactly (a signalling NaN arrives quiet), the tail is (float) of the 16-bit integer
 __device__ __forceinline__ float wire_val32(uint32_t h, size_t i, size_t wend) {
     return i < wend ? __uint_as_float(f16_to_f32(h)) : (float)h;
 }

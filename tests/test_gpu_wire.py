@@ -1,7 +1,8 @@
 """GPU parity of the wire format (engine/comm_manager.cpp:486-590) through the
 C-ABI (``stg_wire_encode_device`` / ``stg_wire_decode_device``) against the
-oracle restatement, which tests/test_wire_oracle.py pins to the x86
-instruction semantics of the reference's casts.  Bit-exact on every byte.
+oracle restatement, which tests/test_wire_isa_host.py pins to the x86
+instructions of the reference's casts (tests/test_gpu_wire_exhaustive.py holds
+the device to them directly, on every boundary value).  Bit-exact on every byte.
 """
 from __future__ import annotations
 

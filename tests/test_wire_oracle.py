@@ -11,6 +11,12 @@ tails' C conversions (the float -> uint16_t tail is GCC's vcvttss2si r32 + a
 16-bit store, read from the -O3 -march=broadwell object code of the same
 construct).  Parity of the wire format is therefore pinned by ISA semantics,
 not by reference output.
+
+numpy's float16 cast is the instruction except on NaNs: it leaves a signalling
+NaN signalling, where vcvtps2ph and vcvtph2ps set the quiet bit, so the model
+patches NaNs in both directions.  tests/test_wire_isa_host.py compares the
+oracle with the executed instructions themselves, over every binary16 word and
+every rounding boundary; this module stays as the independent second model.
 """
 from __future__ import annotations
 
@@ -32,6 +38,9 @@ def _model_encode(idx, val, flag):
     if flag & 2:
         with np.errstate(invalid="ignore", over="ignore"):
             wv = val.astype(np.float16).view(np.uint16).copy()
+            # numpy's cast keeps a signalling NaN signalling (0x7f802000 -> 0x7c01); vcvtps2ph quiets it
+            nan, u = np.isnan(val), val.view(np.uint32)
+            wv[nan] = (((u[nan] >> 16) & 0x8000) | 0x7E00 | ((u[nan] >> 13) & 0x3FF)).astype(np.uint16)
             t = np.full(n, np.int32(-2**31), np.int32)
             ok = np.isfinite(val) & (val > -2147483904.0) & (val < 2147483648.0)
             t[ok] = np.trunc(val[ok]).astype(np.int64).astype(np.int32)
@@ -51,6 +60,9 @@ def _model_decode(wi, wv, flag):
         idx = wi.copy()
     if flag & 2:
         val = wv.view(np.float16).astype(np.float32)
+        nan = (wv & 0x7FFF) > 0x7C00  # vcvtph2ps widens a NaN quiet: sign, payload << 13, quiet bit set
+        val.view(np.uint32)[nan] = ((wv[nan].astype(np.uint32) & 0x8000) << 16) | 0x7FC00000 | \
+            ((wv[nan].astype(np.uint32) & 0x3FF) << 13)
         val[se:] = wv[se:].astype(np.float32)
     else:
         val = wv.copy()
@@ -66,7 +78,13 @@ def _inputs(n, seed, idx_hi):
     m = min(n, specials.size)
     pos = rng.choice(n, m, replace=False) if n else np.zeros(0, np.int64)
     val[pos] = specials[:m]
+    if n > specials.size:  # one signalling float32 NaN; numpy's float16 cast would keep it signalling
+        val.view(np.uint32)[np.setdiff1d(np.arange(n), pos)[0]] = 0x7F802000
     return idx, val
+
+
+# signalling binary16 NaNs as received value words: the widening must quiet them
+SNAN_WORDS = np.array([0x7C01, 0xFDFF], np.uint16)
 
 
 @pytest.mark.parametrize("n", [0, 1, 7, 8, 9, 16, 17, 100, 4099, 65535])
@@ -82,6 +100,13 @@ def test_wire_oracle_matches_isa_model(oracle, n, flag):
     ei, ev = _model_decode(mi, mv, flag)
     assert np.array_equal(di, ei)
     assert np.array_equal(dv.view(np.uint32), ev.view(np.uint32))
+    if flag & 2 and n >= 2:  # the same stream with signalling NaN words in its first two slots
+        wv, mv = wv.copy(), mv.copy()
+        wv[:2] = mv[:2] = SNAN_WORDS
+        dv, ev = oracle.wire_decode(wi, wv, flag)[1], _model_decode(mi, mv, flag)[1]
+        assert np.array_equal(dv.view(np.uint32), ev.view(np.uint32))
+        if n > 9:
+            assert dv.view(np.uint32)[:2].tolist() == [0x7FC02000, 0xFFFFE000]
 
 
 def test_wire_flag_rule(oracle):
