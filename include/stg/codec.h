@@ -76,7 +76,11 @@ int stg_codec_compress_host(stg_codec_t h, const char *key, const float *src, si
  * 2 bytes for a 16-bit wire-form output): any such address gives the same
  * results and nothing outside [d_idx, d_idx + idx_cap), [d_val, d_val +
  * idx_cap) is written.  16-byte alignment of all three selects the vector
- * emission (the fast path); top-k reads a 16-byte aligned d_src by float4. */
+ * emission (the fast path); top-k reads a 16-byte aligned d_src by float4.
+ * k and the capacities may differ from call to call on one key (the engine's
+ * configure_compression_ratio): the key's state is carried over as the
+ * reference carries it, and every call gives the reference's stream for the
+ * state it meets (tests/test_gpu_ratio.py). */
 int stg_codec_compress_device(stg_codec_t h, const char *key, const float *d_src, size_t n, uint32_t k,
                               uint32_t *d_idx, size_t idx_cap, float *d_val, size_t val_cap,
                               int32_t idx_offset, uint32_t *d_count, void *stream);
