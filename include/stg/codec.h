@@ -250,8 +250,11 @@ int stg_codec_check(stg_codec_t h);
  * format's u16 saturation -- the last occurrence wins), summed, divided by
  * `world`, and gathered at the union of indices (one entry per index,
  * unique1d :14-24).  world > 1: output index-ascending, d_dense (n floats,
- * zero) and d_mark (n bytes, zero, 16-byte aligned) are caller scratch and
- * are left zero.  world == 1: no dense scratch; the winners in stream order.
+ * zero, 16-byte aligned) and d_mark (n bytes, zero, 16-byte aligned) are
+ * caller scratch and are left zero; a misaligned one is refused
+ * (STG_ERR_INVALID) by every MERGE entry, the tasks of a batched call
+ * included.  world == 1: no dense scratch (neither pointer is looked at); the
+ * winners in stream order.
  * Indices >= n are dropped.  *d_out_count (device) gets the union size
  * (0xffffffff after a device failure).  Internal scratch is kept per (device,
  * stream) for reuse: 4 B per element of the largest n seen (8 B when world >

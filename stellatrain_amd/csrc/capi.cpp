@@ -1265,6 +1265,8 @@ static int merge_check(const MergeCall &c) {
     }
     if (c.world > 1 && (!c.dense || !c.mark)) return fail(STG_ERR_INVALID, "dense/mark scratch required for world > 1");
     if (c.world > 1 && (reinterpret_cast<uintptr_t>(c.mark) & 15u)) return fail(STG_ERR_INVALID, "mark scratch must be 16-byte aligned");
+    // the emission reads and zeroes a lane's 16 dense floats as four float4
+    if (c.world > 1 && (reinterpret_cast<uintptr_t>(c.dense) & 15u)) return fail(STG_ERR_INVALID, "dense scratch must be 16-byte aligned");
     return STG_OK;
 }
 

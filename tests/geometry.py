@@ -29,6 +29,7 @@ from stellatrain_amd.synth import D1, D2, seed_for, synth
 # (0xffa5ffa5) and as float16, an index past any bucket as uint32 / uint16.  A
 # source guard that leaks into a line sum poisons it.
 SENTINEL16 = 0xFFA5
+SENTINEL8 = 0xA5               # around 1-byte elements (the MERGE marks): a set mark
 
 PHASES4 = (0, 4, 8, 12)        # 4-byte elements: every dword phase of a 16-byte word
 PHASES2 = (0, 2, 6, 8, 14)     # 16-bit wire outputs
@@ -37,17 +38,24 @@ PHASES2 = (0, 2, 6, 8, 14)     # 16-bit wire outputs
 def carve(torch, gpu, numel, dtype, phase_bytes, guard=64):
     """A contiguous view of `numel` elements of `dtype` whose address is
     `phase_bytes` past a 16-byte boundary, inside a larger allocation filled
-    with SENTINEL16, at least `guard` elements of it on either side.  The
-    allocation travels with the view (``view._carve``) for assert_guards."""
+    with SENTINEL16 (SENTINEL8 around 1-byte elements), at least `guard`
+    elements of it on either side.  The allocation travels with the view
+    (``view._carve``) for assert_guards."""
     item = torch.empty(0, dtype=dtype).element_size()
-    assert item in (2, 4) and phase_bytes % item == 0 and 0 <= phase_bytes < 16
-    w = item // 2                                  # 16-bit words per element
+    assert item in (1, 2, 4) and phase_bytes % item == 0 and 0 <= phase_bytes < 16
+    # the allocation is one of 16-bit words, or of SENTINEL8 bytes around 1-byte
+    # elements (a buffer of an odd number of bytes ends inside a word)
+    unit = min(item, 2)
+    w = item // unit                               # words (bytes) per element
     lead = (guard * item + 15) // 16 * 16          # bytes ahead of the 16-byte boundary the phase counts from
-    total = (lead + 16 + numel * item + guard * item + 16) // 2
-    raw = torch.full((total,), SENTINEL16 - 0x10000, dtype=torch.int16, device=gpu)
+    total = (lead + 16 + numel * item + guard * item + 16) // unit
+    if unit == 2:
+        raw = torch.full((total,), SENTINEL16 - 0x10000, dtype=torch.int16, device=gpu)
+    else:
+        raw = torch.full((total,), SENTINEL8, dtype=torch.uint8, device=gpu)
     base = raw.data_ptr()
-    lo = (lead + (-base) % 16 + phase_bytes) // 2  # first word of the view
-    assert (base + 2 * lo) % 16 == phase_bytes and lo >= guard * w
+    lo = (lead + (-base) % 16 + phase_bytes) // unit  # first word of the view
+    assert (base + unit * lo) % 16 == phase_bytes and lo >= guard * w
     hi = lo + numel * w
     assert total - hi >= guard * w
     view = raw[lo:hi].view(dtype)
@@ -63,11 +71,13 @@ def assert_guards(view, what=""):
     """Every word of the allocation outside the view still holds the sentinel."""
     raw, lo, hi = view._carve
     for side, g in (("before", raw[:lo]), ("after", raw[hi:])):
-        a = g.cpu().numpy().view(np.uint16)
-        bad = np.flatnonzero(a != SENTINEL16)
+        a = g.cpu().numpy()
+        bits = 8 * a.itemsize
+        a = a.view(np.uint16 if bits == 16 else np.uint8)
+        bad = np.flatnonzero(a != (SENTINEL16 if bits == 16 else SENTINEL8))
         if bad.size:
-            raise AssertionError(f"{what}: {bad.size} 16-bit words {side} the buffer were overwritten, first at word "
-                                 f"{int(bad[0])} of {a.size} (0x{int(a[bad[0]]):04x})")
+            raise AssertionError(f"{what}: {bad.size} {bits}-bit words {side} the buffer were overwritten, first at "
+                                 f"word {int(bad[0])} of {a.size} (0x{int(a[bad[0]]):04x})")
 
 
 # ---------------------------------------------------------------------------

@@ -94,6 +94,63 @@ def test_argument_checks_need_no_device():
     assert L.stg_wire_decode_batch_device(rx, 1, None) == 0
 
 
+def test_misaligned_scratch_is_refused_for_world_above_one():
+    """d_mark and d_dense are read as 16-byte vectors by the world > 1 emission:
+    each is refused at every other phase, by every MERGE entry (the batched
+    tasks included), with an error that names the buffer; world 1 looks at
+    neither."""
+    from stellatrain_amd._capi import StgMergeTask, StgRankStream, lib
+    L = lib()
+    buf = (C.c_uint8 * 128)()
+    p16 = (C.addressof(buf) + 15) & ~15
+    out = C.c_void_p(p16)
+    two = (StgRankStream * 2)(StgRankStream(p16, p16, 1), StgRankStream(p16, p16, 3))
+    one = (StgRankStream * 1)(StgRankStream(p16, p16, 0))
+    h = C.c_void_p()
+    assert L.stg_sgd_create(0, 0.1, 0.9, 0.0, 0.0, 0, 0, C.byref(h)) == 0
+    a = C.c_void_p()
+    assert L.stg_adam_create(0, 1e-3, 0.9, 0.999, 1e-8, 0.0, 0, 0, C.byref(a)) == 0
+
+    def entries(ranks, world, dense, mark):
+        """Every MERGE entry on the same scratch arguments, before any device call."""
+        task = (StgMergeTask * 1)(StgMergeTask(b"w", p16, 100, ranks, 4, world, dense, mark, p16, p16, p16))
+        d, m = C.c_void_p(dense), C.c_void_p(mark)
+        yield "wire", L.stg_scatter_merge_wire_device(ranks, 4, world, 100, d, m, out, out, out, None)
+        yield "decoded", L.stg_scatter_merge_device(out, out, 4, world, 100, d, m, out, out, out, None)
+        yield "sgd", L.stg_merge_optimize_sgd_wire_device(h, b"w", out, 100, ranks, 4, world, d, m, out, out, out, None)
+        yield "sgd decoded", L.stg_merge_optimize_sgd_device(h, b"w", out, 100, out, out, 4, world, d, m, out, out, out,
+                                                             None)
+        yield "adam", L.stg_merge_optimize_adam_wire_device(a, b"w", out, 100, ranks, 4, world, d, m, out, out, out,
+                                                            None)
+        yield "sgd batch", L.stg_merge_optimize_sgd_batch_device(h, task, 1, None)
+        yield "adam batch", L.stg_merge_optimize_adam_batch_device(a, task, 1, None)
+
+    for off in (1, 4, 8, 12, 15):
+        for entry, rc in entries(two, 2, p16, p16 + off):
+            assert rc == -1, (entry, off)
+            err = L.stg_last_error()
+            assert b"mark" in err and b"aligned" in err and b"dense" not in err, (entry, off, err)
+    for off in (4, 8, 12):  # a float buffer: element-aligned, not 16-byte aligned
+        for entry, rc in entries(two, 2, p16 + off, p16):
+            assert rc == -1, (entry, off)
+            err = L.stg_last_error()
+            assert b"dense" in err and b"aligned" in err and b"mark" not in err, (entry, off, err)
+            assert not entry.endswith("batch") or err.startswith(b"task 0"), err
+    it = C.c_uint32(9)
+    assert L.stg_sgd_get_iter(h, C.byref(it)) == 0 and it.value == 0  # a refused call is no iteration
+    # world 1 uses neither: the same pointers pass these checks.  (An accepted
+    # call needs a device; a batched task is checked in full before any device
+    # call, so the refusal that comes after this one -- the fused step's empty
+    # parameter -- shows that the scratch pointers were let through.)
+    for dense, mark in ((p16 + 4, p16 + 1), (None, None)):
+        task = (StgMergeTask * 1)(StgMergeTask(b"w", p16, 0, one, 4, 1, dense, mark, p16, p16, p16))
+        for f, o in ((L.stg_merge_optimize_sgd_batch_device, h), (L.stg_merge_optimize_adam_batch_device, a)):
+            assert f(o, task, 1, None) != 0
+            err = L.stg_last_error()
+            assert b"empty parameter" in err and b"aligned" not in err, err
+    assert L.stg_sgd_destroy(h) == 0 and L.stg_adam_destroy(a) == 0
+
+
 def test_python_validation_needs_no_device():
     import pytest
     import torch
