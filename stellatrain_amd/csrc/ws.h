@@ -105,8 +105,15 @@ static_assert(LNBIN == 1024, "32 lines x 32 words");
 constexpr uint32_t CREW_BINS = 8192;
 struct CrewCtl {
     uint32_t hist[CREW_BINS];  // zeroed by the bucket's phase Z
-    uint32_t beta, nL, status, P, tail_rank, op, pad[2];
+    // The hand-off words on a 128-byte line of their own.  Packed behind hist
+    // (32 bytes), they shared a line with the next slot's hist[0 .. 23]: with
+    // two buckets in the crew, phase C of bucket j + 1 loads that line (an sc1
+    // load into LDS, not into registers) while phase D of bucket j has yet to
+    // store P, tail_rank and op, and an emission unit of bucket j on that XCD
+    // could then read the previous call's P and skip its share.
+    uint32_t beta, nL, status, P, tail_rank, op, pad[26];
 };
+static_assert(sizeof(CrewCtl) % 128 == 0 && offsetof(CrewCtl, beta) % 128 == 0, "hand-off words on their own line");
 
 // top-k steered by the key's last k-th magnitude (topk1.hip): per-call control
 // block, two copies by call tag parity (each call zeroes the next call's), and

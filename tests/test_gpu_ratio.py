@@ -23,6 +23,7 @@ import pytest
 import publish_cases as P
 import ratio_cases as rc
 import wire_merge_cases as W
+from chain_helpers import OPTS, Optim, debug_words, merged, oracle_send, state_bits, u
 from geometry import assert_guards, carve
 from parity import assert_same_stream, assert_topk_values, fbits
 from stellatrain_amd.synth import D1, D3, seed_for, synth
@@ -34,23 +35,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 WINDOW_WORDS = (44, 45, 48, 49, 52, 56, 57, 58)
 # ... or past it: the crew (53), the literal heap (59)
 WIDE_WORDS = (53, 59)
-
-
-def _u(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint16) if a.itemsize == 2 else a.view(np.uint32)
-
-
-def _state_bits(s):
-    return [fbits(v) for v in s]
-
-
-def _words(comp, gpu):
-    import torch
-    from stellatrain_amd._capi import check, lib
-    w = (C.c_uint32 * 64)()
-    check(lib().stg_codec_debug_words(comp._h, C.c_void_p(torch.cuda.current_stream(gpu).cuda_stream), w, 64))
-    return list(w)
 
 
 # ---------------------------------------------------------------------------
@@ -65,7 +49,7 @@ def _one_key(gpu, oracle, n, dist=D1, param=0, bucket=rc.SEED_BUCKET, ratios=Non
     key = "5@weight"
     d = torch.empty(n, dtype=torch.float32, device=gpu)
     report, wrong = [], []
-    w0 = _words(comp, gpu)
+    w0 = debug_words(comp, gpu)
     try:
         for it, r, k in rc.schedule(n, ratios=ratios):
             x = rc.ratio_input(n, it, dist, param, bucket)
@@ -85,9 +69,9 @@ def _one_key(gpu, oracle, n, dist=D1, param=0, bucket=rc.SEED_BUCKET, ratios=Non
             what = f"n {n}, call {it}: ratio {r}, k {k}"
             assert cnt == co, what
             assert_same_stream(idx.cpu().numpy().view(np.uint32), val.cpu().numpy(), io, vo, co, what)
-            assert _state_bits(comp.state(key)) == _state_bits(so), what
-            assert np.array_equal(_u(d.cpu().numpy()), _u(x)), "the bucket changed: " + what
-            w1 = _words(comp, gpu)
+            assert state_bits(comp.state(key)) == state_bits(so), what
+            assert np.array_equal(u(d.cpu().numpy()), u(x)), "the bucket changed: " + what
+            w1 = debug_words(comp, gpu)
             dw = [a - b for a, b in zip(w1, w0)]
             w0 = w1
             row = {"it": it, "ratio": r, "k": k, "ms": round(ms, 3), "regime": "-"}
@@ -178,15 +162,15 @@ def test_tv16_batched_staggered(gpu, oracle, n, entry):
             for j, ((key, s, k, di, dv), (co, (wi, wv), so, after)) in enumerate(zip(items, exp)):
                 what = f"{entry}, n {n}, launch {step}, key {j}: ratio {row[j][3]}, k {k}"
                 assert got[j] == co, what
-                ig, vg = _u(di.cpu().numpy()), _u(dv.cpu().numpy())
-                bad = np.flatnonzero((ig[:co] != _u(wi)) | (vg[:co] != _u(wv)))
+                ig, vg = u(di.cpu().numpy()), u(dv.cpu().numpy())
+                bad = np.flatnonzero((ig[:co] != u(wi)) | (vg[:co] != u(wv)))
                 assert not bad.size, f"{what}: {bad.size} of {co} pairs differ, first at {int(bad[0])}"
-                assert _state_bits(comp.state(key)) == _state_bits(so), what
-                assert np.array_equal(_u(s.cpu().numpy()), _u(after)), "bucket: " + what
+                assert state_bits(comp.state(key)) == state_bits(so), what
+                assert np.array_equal(u(s.cpu().numpy()), u(after)), "bucket: " + what
                 if entry == "residual":
-                    assert np.array_equal(_u(res_d[j].cpu().numpy()), _u(after)), "residual: " + what
+                    assert np.array_equal(u(res_d[j].cpu().numpy()), u(after)), "residual: " + what
         comp.check_device()
-        w = _words(comp, gpu)
+        w = debug_words(comp, gpu)
         print(entry, n, "scan_ranked", w[44:46], "wide", w[52:56], "paths", w[56:60])
     finally:
         oracle.tv16_free(ho)
@@ -224,9 +208,9 @@ def test_tv16_d3_batched(gpu, oracle):
                 what = f"D3 batched, call {it}, key {j}: ratio {r}, k {k}"
                 assert counts[j] == co, what
                 assert_same_stream(di.cpu().numpy().view(np.uint32), dv.cpu().numpy(), io, vo, co, what)
-                assert _state_bits(comp.state(key)) == _state_bits(so), what
+                assert state_bits(comp.state(key)) == state_bits(so), what
         comp.check_device()
-        w = _words(comp, gpu)
+        w = debug_words(comp, gpu)
         print("D3 batched: wide", w[52:56], "paths", w[56:60])
     finally:
         oracle.tv16_free(ho)
@@ -321,7 +305,7 @@ def test_topk_k_schedule(gpu, oracle, bug_compat):
     comp = TopkCompressor(exact=not bug_compat)
     n = rc.TOPK_N
     d = torch.empty(n, dtype=torch.float32, device=gpu)
-    w0 = _words(comp, gpu)
+    w0 = debug_words(comp, gpu)
     for c, k in enumerate(rc.topk_ks(n)):
         x = rc.ratio_input(n, c, bucket=rc.TOPK_SEED_BUCKET)
         d.copy_(torch.from_numpy(x))
@@ -341,7 +325,7 @@ def test_topk_k_schedule(gpu, oracle, bug_compat):
                 assert_topk_values(val.cpu().numpy(), vo)
             else:
                 assert_same_stream(idx.cpu().numpy().view(np.uint32), val.cpu().numpy(), io, vo, k, what)
-        w = _words(comp, gpu)
+        w = debug_words(comp, gpu)
         print(what, "band hits (38)", w[38] - w0[38], "select (39)", w[39] - w0[39])
         if c == 0:
             assert (w[38] - w0[38], w[39] - w0[39]) == (0, 1), w[36:40]  # the first call: the select's way
@@ -357,17 +341,6 @@ SIDE_RATIOS = rc.RATIOS[:12]
 
 def _send_grads(n, j, it, N=2, rank=0):
     return [synth(n, seed_for(940 + 10 * j + 100 * rank + s, it), D1) for s in range(N)]
-
-
-def _oracle_send(oracle, ho, key, srcs, resid, k, flag):
-    """gather_add -> tv16_compress -> error feedback -> wire_encode."""
-    x = srcs[0].copy()
-    for r in range(len(srcs)):
-        oracle.gather_add([x] + srcs[1:], resid, r)
-    co, io, vo = oracle.tv16_compress(ho, key, x, k)
-    wi, wv = oracle.wire_encode(io[:co], vo[:co], flag)
-    x[io[:k]] = 0
-    return x, co, wi, wv
 
 
 @pytest.mark.parametrize("fp16_values", [False, True])
@@ -397,15 +370,15 @@ def test_send_buckets_ratio(gpu, oracle, fp16_values):
             for j, n in enumerate(SEND_NS):
                 k, flag = rc.merge_k(n, r), wire_flag(n, fp16_values)
                 what = f"send, iteration {it}: ratio {r}, n {n}, k {k}, flag {flag}"
-                x, co, wi, wv = _oracle_send(oracle, ho, keys[j], srcs[j], res_np[j], k, flag)
+                x, co, wi, wv = oracle_send(oracle, ho, keys[j], srcs[j], res_np[j], k, flag)
                 res_np[j] = x.copy()
                 di, dv, fl = streams[j]
                 assert fl == flag and di.numel() == k and cg[j] == co, what
-                assert np.array_equal(_u(g[j][0].cpu().numpy()), _u(x)), "grad[0]: " + what
-                assert np.array_equal(_u(res[j].cpu().numpy()), _u(x)), "residual: " + what
-                assert np.array_equal(_u(di.cpu().numpy())[:co], _u(wi)), "wire indices: " + what
-                assert np.array_equal(_u(dv.cpu().numpy())[:co], _u(wv)), "wire values: " + what
-                assert _state_bits(eng.compressor().state(keys[j])) == _state_bits(oracle.tv16_state(ho, keys[j])), what
+                assert np.array_equal(u(g[j][0].cpu().numpy()), u(x)), "grad[0]: " + what
+                assert np.array_equal(u(res[j].cpu().numpy()), u(x)), "residual: " + what
+                assert np.array_equal(u(di.cpu().numpy())[:co], u(wi)), "wire indices: " + what
+                assert np.array_equal(u(dv.cpu().numpy())[:co], u(wv)), "wire values: " + what
+                assert state_bits(eng.compressor().state(keys[j])) == state_bits(oracle.tv16_state(ho, keys[j])), what
         eng.compressor().check_device()
     finally:
         oracle.tv16_free(ho)
@@ -414,10 +387,6 @@ def test_send_buckets_ratio(gpu, oracle, fp16_values):
 # ---------------------------------------------------------------------------
 # receiving side: per_rank shrinks and grows under persistent optimizer state
 # ---------------------------------------------------------------------------
-OPTS = {"sgd": dict(lr=0.05, momentum=0.9, nesterov=True, weight_decay=0.01, smart_momentum=True),
-        "adam": dict(lr=0.01, weight_decay=0.01)}
-
-
 def _rank_streams_np(oracle, hos, name, n, j, it, per_rank, flag):
     """One wire stream per rank: the oracle's thresholdv16 stream of that
     rank's synthetic gradient (whole lines of 16 consecutive indices, ranks
@@ -431,51 +400,9 @@ def _rank_streams_np(oracle, hos, name, n, j, it, per_rank, flag):
     return out
 
 
-class _Optim:
-    """A device optimizer and its oracle twin over named parameters."""
-
-    def __init__(self, oracle, kind):
-        from stellatrain_amd import SparseAdam, SparseSGD
-        self.oracle, self.kind = oracle, kind
-        self.dev = (SparseSGD if kind == "sgd" else SparseAdam)(**OPTS[kind])
-        self.h = oracle.sgd_new(**OPTS[kind]) if kind == "sgd" else oracle.adam_new(**OPTS[kind])
-
-    def apply_oracle(self, name, po, ev, ei):
-        (self.oracle.sgd_apply if self.kind == "sgd" else self.oracle.adam_apply)(self.h, name, po, ev, ei)
-
-    def compare(self, name, pd, po, what):
-        n, o = po.size, self.oracle
-        assert np.array_equal(_u(pd.cpu().numpy()), _u(po)), "parameter: " + what
-        if self.kind == "sgd":
-            assert np.array_equal(_u(self.dev.momentum_buffer(name, n)), _u(o.sgd_momentum(self.h, name, n))), \
-                "momentum: " + what
-            assert np.array_equal(self.dev.last_buffer(name, n), o.sgd_last(self.h, name, n)), "last touched: " + what
-            assert self.dev.iteration == o.sgd_iter(self.h), what
-        else:
-            sd, so = self.dev.state(name, n), o.adam_state(self.h, name, n)
-            assert np.array_equal(_u(sd[0]), _u(so[0])), "m: " + what
-            assert np.array_equal(_u(sd[1]), _u(so[1])), "v: " + what
-            assert sd[3] == so[3], "tick: " + what
-
-    def check(self):
-        self.dev.check() if self.kind == "sgd" else self.dev.check_device()
-
-    def close(self):
-        (self.oracle.sgd_free if self.kind == "sgd" else self.oracle.adam_free)(self.h)
-
-
-def _merged(out):
-    oi, ov, cnt = out
-    c = int(cnt.cpu().numpy().view(np.uint32)[0])
-    assert c != 0xffffffff and c <= oi.numel()
-    i, v = oi.cpu().numpy().view(np.uint32)[:c], ov.cpu().numpy().view(np.uint32)[:c]
-    o = np.argsort(i, kind="stable")
-    return i[o], v[o]
-
-
 def _check_replicas(param, rep32, rep16, what):
     p = param.cpu().numpy()
-    assert np.array_equal(_u(rep32.cpu().numpy()), _u(p)), "float32 replica: " + what
+    assert np.array_equal(u(rep32.cpu().numpy()), u(p)), "float32 replica: " + what
     import torch
     assert np.array_equal(rep16.view(torch.int16).cpu().numpy().view(np.uint16), P.f32_to_bf16_bits(p)), \
         "bfloat16 replica: " + what
@@ -491,7 +418,7 @@ def test_merge_optimize_publish_ratio(gpu, oracle, kind, world):
     import torch
     from stellatrain_amd import MergeTasks, PublishTasks, publish_params, wire_flag
     from stellatrain_amd.engine import scatter_merge_check
-    opt = _Optim(oracle, kind)
+    opt = Optim(oracle, kind)
     hos = [oracle.tv16_new() for _ in range(world)]
     names = [f"m{j}@weight" for j in range(len(SEND_NS))]
     p0 = [synth(n, seed_for(950 + j, 0), D1) * np.float32(100) for j, n in enumerate(SEND_NS)]
@@ -520,9 +447,9 @@ def test_merge_optimize_publish_ratio(gpu, oracle, kind, world):
             for j, n in enumerate(SEND_NS):
                 what = f"{kind}, world {world}, iteration {it}: ratio {r}, n {n}, per_rank {rc.merge_k(n, r, world)}"
                 ei, ev = exp[j]
-                gi, gv = _merged(got[j])
+                gi, gv = merged(got[j])
                 assert gi.size == ei.size, "merged count: " + what
-                assert np.array_equal(gi, ei) and np.array_equal(gv, _u(ev)), "merged stream: " + what
+                assert np.array_equal(gi, ei) and np.array_equal(gv, u(ev)), "merged stream: " + what
                 opt.apply_oracle(names[j], po[j], ev, ei)
             for j, n in enumerate(SEND_NS):  # (the optimizer's iteration count is shared by the names)
                 what = f"{kind}, world {world}, iteration {it}: ratio {r}, n {n}, per_rank {rc.merge_k(n, r, world)}"
@@ -594,21 +521,21 @@ def test_closed_loop_two_ranks(gpu, oracle):
                 what = f"closed loop, iteration {it}: ratio {r}, n {n}, per_rank {ks[j]}"
                 wire = []
                 for q in range(R):
-                    x, co, wi, wv = _oracle_send(oracle, ho[q], keys[j], srcs[q][j], res_np[q][j], ks[j], flags[j])
+                    x, co, wi, wv = oracle_send(oracle, ho[q], keys[j], srcs[q][j], res_np[q][j], ks[j], flags[j])
                     res_np[q][j] = x.copy()
                     assert int(sent[q][1].cpu().numpy()[j]) == co == ks[j], what
-                    assert np.array_equal(_u(res[q][j].cpu().numpy()), _u(x)), f"residual of rank {q}: " + what
-                    assert np.array_equal(_u(sent[q][0][j][0].cpu().numpy())[:co], _u(wi)), f"wire of rank {q}: " + what
-                    assert np.array_equal(_u(sent[q][0][j][1].cpu().numpy())[:co], _u(wv)), f"wire of rank {q}: " + what
-                    assert _state_bits(eng[q].compressor().state(keys[j])) == \
-                        _state_bits(oracle.tv16_state(ho[q], keys[j])), f"threshold of rank {q}: " + what
+                    assert np.array_equal(u(res[q][j].cpu().numpy()), u(x)), f"residual of rank {q}: " + what
+                    assert np.array_equal(u(sent[q][0][j][0].cpu().numpy())[:co], u(wi)), f"wire of rank {q}: " + what
+                    assert np.array_equal(u(sent[q][0][j][1].cpu().numpy())[:co], u(wv)), f"wire of rank {q}: " + what
+                    assert state_bits(eng[q].compressor().state(keys[j])) == \
+                        state_bits(oracle.tv16_state(ho[q], keys[j])), f"threshold of rank {q}: " + what
                     wire.append((wi, wv, flags[j]))
                 ei, ev = W.expected(oracle, wire, ks[j], n)[2:4]
                 oracle.sgd_apply(hs, keys[j], po[j], ev, ei)
                 for q in range(R):
-                    gi, gv = _merged(outs[q][j])
-                    assert np.array_equal(gi, ei) and np.array_equal(gv, _u(ev)), f"merged stream on rank {q}: " + what
-                    assert np.array_equal(_u(pd[q][j].cpu().numpy()), _u(po[j])), f"parameter on rank {q}: " + what
+                    gi, gv = merged(outs[q][j])
+                    assert np.array_equal(gi, ei) and np.array_equal(gv, u(ev)), f"merged stream on rank {q}: " + what
+                    assert np.array_equal(u(pd[q][j].cpu().numpy()), u(po[j])), f"parameter on rank {q}: " + what
                     assert np.array_equal(rep[q][j].view(torch.int16).cpu().numpy().view(np.uint16),
                                           P.f32_to_bf16_bits(po[j])), f"replica on rank {q}: " + what
         for q in range(R):
