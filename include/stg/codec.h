@@ -613,6 +613,70 @@ int stg_param_publish_batch_device(const stg_publish_task_t *tasks, size_t ntask
  * a null array with ntasks > 0 or num_cu < 1). */
 int stg_debug_publish_launches(const uint32_t *idx_caps, size_t ntasks, int num_cu);
 
+/* Gather-add from bf16 / fp16 gradient sources.  The node's other GPUs may
+ * hold 16-bit model replicas (stg_param_publish_batch_device keeps them
+ * current) and so produce 16-bit gradients; these entry points read them as
+ * they are, widened in the load, instead of from fp32 temporaries. */
+typedef struct stg_grad_src {
+    const void *d_grad;            /* n elements of `dtype`, aligned to the element size          */
+    int dtype;                     /* STG_DT_*                                                    */
+} stg_grad_src_t;                  /* 16 bytes on LP64: d_grad at 0, dtype at 8                   */
+
+/* stg_gather_add_device / stg_merge_gather_compress_device /
+ * stg_merge_send_batch_device with typed sources.  Per element, in the
+ * reference's order (cpu_gather.cpp:59-87):
+ *   acc = term0; if d_residual: acc += d_residual[e];
+ *   for s = 1 .. N-1: acc += widen(srcs[s][e]);  d_grad0[e] = acc
+ * term0 is d_grad0[e] (the bucket, bucket.d_src in the codec forms) when
+ * srcs[0].d_grad is null, or STG_DT_F32 and equal to the bucket: today's
+ * in-place form.  Otherwise term0 = widen(srcs[0][e]) and the bucket is
+ * write-only, so a 16-bit local gradient needs no widening copy.  The bucket
+ * and the residual stay fp32.  widen is the identity for STG_DT_F32,
+ * bits << 16 for STG_DT_BF16, and for STG_DT_F16 the exact conversion
+ * (vcvtph2ps: subnormals kept, -0 keeps its sign); a NaN source yields a NaN
+ * of unspecified payload.  Sources are never written; nothing outside the
+ * slice (stg_gather_slice) of the bucket is.
+ *   Equivalence: widening is exact, so after a typed call the bucket, the
+ * residual, the wire stream, the count and the key's AIMD state are bitwise
+ * those of the fp32 entry point run on fp32 copies of the sources (the bucket
+ * preloaded with the widened copy of a typed term0).
+ *   stg_merge_send_batch_typed_device: srcs[i] is null -- task i then uses its
+ * fp32 d_grads exactly as stg_merge_send_batch_device -- or a host array of
+ * tasks[i].num_gpus typed sources, and tasks[i].d_grads is ignored (with
+ * num_gpus == 1 the array holds only term0).  thresholdv16 only.
+ *   Routing: a call whose sources are all fp32 and in place runs the fp32
+ * entry point's launches.  Otherwise 16-bit sources load 16 (or 8) bytes per
+ * lane and fp32 streams 16, in lane groups of 8 (or 4) elements, wherever one
+ * head length brings every pointer of the task to its alignment; else every
+ * element is a scalar lane (stg_debug_gather_plan).  A lone task of
+ * 2^22..2^24 elements with a 16-bit source or a typed term0 runs the typed
+ * gather-add pass and then the plain scan instead of the scan that sums fp32
+ * sources in its own pass; the results are the same bits.  Launch counts are
+ * those of the fp32 entry points.
+ *   All or nothing, as the fp32 entry points: every check precedes any device
+ * call or key-state change and the send batch names the task index in
+ * stg_last_error().  STG_ERR_INVALID: what the fp32 twin refuses (a null
+ * `srcs` where it refuses a null d_grads), an unknown dtype, a source pointer
+ * not aligned to its element size, a null source at index >= 1 with n > 0.
+ * Peer (xGMI) sources have not been run on hardware; tests and timings use
+ * sources on the bucket's GPU.  Async on `stream`. */
+int stg_gather_add_typed_device(float *d_grad0, const float *d_residual, const stg_grad_src_t *srcs, int num_gpus,
+                                uint64_t n, int local_rank, void *stream);
+int stg_merge_gather_compress_typed_device(stg_codec_t h, const stg_bucket_t *bucket, float *d_residual,
+                                           const stg_grad_src_t *srcs, int num_gpus, void *stream);
+int stg_merge_send_batch_typed_device(stg_codec_t h, const stg_send_task_t *tasks,
+                                      const stg_grad_src_t *const *srcs, size_t ntasks, void *stream);
+/* Diagnostics, plain host arithmetic (no device): the plan a typed gather-add
+ * takes for `nstreams` (1..18) streams -- the bucket, the residual and the
+ * sources -- of element types dtypes[i], addrs[i] being stream i's address at
+ * the first element of the range of n elements.  *width: elements per lane
+ * group, 8 or 4, or 0 when no head length aligns every stream (all scalar,
+ * *head = 0); *head: the scalar elements before the first group, < *width and
+ * <= n.  After the head an fp32 stream is 16-byte aligned and a 16-bit stream
+ * 2 * width bytes aligned (when head < n). */
+int stg_debug_gather_plan(const uint64_t *addrs, const int *dtypes, size_t nstreams, uint64_t n, uint32_t *width,
+                          uint32_t *head);
+
 /* Synthetic fp32 buckets from the integer-only generator of SURVEY 8(d)
  * (dist 0 = D1, 1 = D2 heavy tail, 2 = D3 zeros with prob param/1e4);
  * bit-identical to oracle/stg_oracle.cpp:orc_synth_fill. */

@@ -5,7 +5,8 @@ thresholdv16 / threshold-v / Top-k codecs, the MERGE decompress and the
 sparse SGD apply, as hand-written HIP kernels for gfx950 behind the C-ABI in
 include/stg/codec.h.  See DESIGN.md.
 """
-from ._capi import CodecError, StgMergeTask, StgPublishTask, StgReplica, StgSendTask, lib  # noqa: F401
+from ._capi import (CodecError, StgGradSrc, StgMergeTask, StgPublishTask, StgReplica, StgSendTask,  # noqa: F401
+                    lib)
 from .compressor import (Compressor, SendTasks, ThresholdvCompressor, ThresholdvCompressor16,  # noqa: F401
                          TopkCompressor, make_compressor)
 from .engine import (CodecEngine, MergeTasks, PublishTasks, SparseAdam, SparseSGD, api_numel, merge_numel, owner_of,  # noqa: F401

@@ -71,6 +71,11 @@ class StgPublishTask(C.Structure):
                 ("idx_cap", C.c_uint32), ("replicas", C.POINTER(StgReplica)), ("nreplicas", C.c_int)]
 
 
+class StgGradSrc(C.Structure):
+    """``stg_grad_src_t``: one typed gradient source of the ``*_typed_device`` gather entry points."""
+    _fields_ = [("d_grad", C.c_void_p), ("dtype", C.c_int)]
+
+
 STG_DT_F32, STG_DT_BF16, STG_DT_F16 = 0, 1, 2
 
 _lib: C.CDLL | None = None
@@ -128,6 +133,14 @@ _SIGS = {
     "stg_gather_slice": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "stg_gather_add_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int,
                                         C.c_void_p]),
+    "stg_gather_add_typed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(StgGradSrc), C.c_int, C.c_uint64,
+                                              C.c_int, C.c_void_p]),
+    "stg_merge_gather_compress_typed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StgGradSrc),
+                                                         C.c_int, C.c_void_p]),
+    "stg_merge_send_batch_typed_device": (C.c_int, [C.c_void_p, C.POINTER(StgSendTask),
+                                                    C.POINTER(C.POINTER(StgGradSrc)), C.c_size_t, C.c_void_p]),
+    "stg_debug_gather_plan": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_size_t, C.c_uint64,
+                                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "stg_wire_flag": (C.c_int, [C.c_uint64, C.c_int]),
     "stg_wire_encode_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),

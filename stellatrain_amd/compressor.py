@@ -25,7 +25,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._capi import CodecError, StgBucket, StgSendTask, check, lib
+from ._capi import (STG_DT_BF16, STG_DT_F16, STG_DT_F32, CodecError, StgBucket, StgGradSrc, StgSendTask, check,
+                    lib)
 
 __all__ = ["Compressor", "SendTasks", "ThresholdvCompressor16", "ThresholdvCompressor", "TopkCompressor", "make_compressor",
            "CodecError"]
@@ -40,22 +41,55 @@ def _stream_ptr(device: int) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def grad_dtype(t):
+    """The ``STG_DT_*`` code of a gradient tensor's dtype (None: not one a gather reads)."""
+    import torch
+    return {torch.float32: STG_DT_F32, torch.bfloat16: STG_DT_BF16, torch.float16: STG_DT_F16}.get(t.dtype)
+
+
+def typed_sources(what: str, grads, bucket):
+    """The ``stg_grad_src_t`` array of a gather's ``grads`` for the
+    ``*_typed_device`` entry points, or None when the fp32 entry point takes
+    them: every tensor float32 and no separate ``bucket``.  ``grads[1:]`` may
+    be float32, bfloat16 or float16; ``grads[0]`` too when ``bucket`` (the
+    float32 tensor the sum is written to) is given -- it is then only read --
+    and must be float32, the bucket itself, otherwise."""
+    dts = [grad_dtype(g) for g in grads]
+    if any(d is None for d in dts):
+        raise ValueError(f"{what}: float32, bfloat16 or float16 gradients expected")
+    if bucket is None:
+        if dts[0] != STG_DT_F32:
+            raise ValueError(f"{what}: a bfloat16 / float16 grads[0] needs a float32 bucket to be written to")
+        if all(d == STG_DT_F32 for d in dts):
+            return None
+    arr = (StgGradSrc * len(grads))()
+    for i, (g, d) in enumerate(zip(grads, dts)):
+        if i or bucket is not None:  # ([0] stays null without a bucket: in place)
+            arr[i] = StgGradSrc(g.data_ptr(), d)
+    return arr
+
+
 class SendTasks:
     """A prebuilt ``stg_send_task_t`` array: the iteration's sender-side tasks,
     marshalled and validated once and reused by every
     ``Compressor.merge_send_batch_async`` call on the same tensors (a model's
     gradient, residual and send buffers do not move between iterations).  Each
     item is ``(key, grads, k, dst_idx, dst_val, residual, wire_flag[,
-    idx_offset])``: ``grads[0]`` is the bucket, ``residual`` may be None, the
-    dst dtypes follow the flag (int16 / int32 indices, int16 / float32 values).
+    idx_offset[, bucket]])``: ``grads[0]`` is the bucket, ``residual`` may be
+    None, the dst dtypes follow the flag (int16 / int32 indices, int16 / float32
+    values).  ``grads[1:]`` may be float32, bfloat16 or float16 (16-bit model
+    replicas' gradients, read as they are); with ``bucket``, a float32 tensor
+    that receives the sum, ``grads[0]`` may be too and is only read.
     ``counts`` (int32, one per item) receives the pair counts of every call on
-    the array.  The array keeps every tensor it points at alive."""
+    the array.  The array keeps every tensor it points at alive, and the typed
+    source arrays (``srcs``; None when every item is float32 in place)."""
 
     def __init__(self, items, counts=None):
         import torch
         items = list(items)
         self.count = len(items)
         self.array = (StgSendTask * max(self.count, 1))()
+        self.srcs = None
         self.device = items[0][1][0].device if items and len(items[0]) > 1 and len(items[0][1]) else None
         self.counts = counts
         self._keep = []
@@ -67,11 +101,12 @@ class SendTasks:
         if self.counts.numel() < self.count or self.counts.dtype != torch.int32 or not self.counts.is_contiguous():
             raise ValueError("merge_send_batch: counts must be a contiguous int32 tensor, one element per item")
         for j, it in enumerate(items):
-            if not 7 <= len(it) <= 8:
+            if not 7 <= len(it) <= 9:
                 raise ValueError(f"merge_send_batch: item {j}: (key, grads, k, dst_idx, dst_val, residual, wire_flag"
                                  "[, idx_offset]) expected")
             key, grads, k, di, dv, resid, flag = it[:7]
             off = int(it[7]) if len(it) > 7 else 0
+            bucket = it[8] if len(it) > 8 else None
             flag = int(flag)
             grads = list(grads)
             if flag not in (0, 1, 2, 3):
@@ -84,20 +119,29 @@ class SendTasks:
             if dv.numel() < di.numel():
                 raise ValueError(f"merge_send_batch: item {j}: dst_val shorter than dst_idx")
             n = grads[0].numel()
-            srcs = grads + ([resid] if resid is not None else [])
-            if any(t.numel() != n or t.dtype != torch.float32 for t in srcs):
+            f32 = [t for t in (resid, bucket) if t is not None]
+            srcs = grads + f32
+            if any(t.numel() != n for t in srcs) or any(t.dtype != torch.float32 for t in f32) or \
+                    any(grad_dtype(t) is None for t in grads):
                 raise ValueError(f"merge_send_batch: item {j}: float32 gradients and residual of one size")
+            typed = typed_sources(f"merge_send_batch: item {j}", grads, bucket)
             if not all(t.is_contiguous() for t in srcs + [di, dv]):
                 raise ValueError(f"merge_send_batch: item {j}: tensors must be contiguous")
             if not all(t.is_cuda and t.device == dev for t in srcs + [di, dv, self.counts]):
                 raise ValueError(f"merge_send_batch: item {j}: tensors must be on one HIP device")
             kb = key.encode()
-            ptrs = (C.c_void_p * len(grads))(*[t.data_ptr() for t in grads])
-            b = StgBucket(kb, grads[0].data_ptr(), n, int(k), di.data_ptr(), di.numel(), dv.data_ptr(), dv.numel(),
-                          off, self.counts.data_ptr() + 4 * j)
+            ptrs = None
+            if typed is None:
+                ptrs = (C.c_void_p * len(grads))(*[t.data_ptr() for t in grads])
+            else:
+                if self.srcs is None:
+                    self.srcs = (C.POINTER(StgGradSrc) * self.count)()
+                self.srcs[j] = typed
+            b = StgBucket(kb, (grads[0] if bucket is None else bucket).data_ptr(), n, int(k), di.data_ptr(),
+                          di.numel(), dv.data_ptr(), dv.numel(), off, self.counts.data_ptr() + 4 * j)
             self.array[j] = StgSendTask(b, resid.data_ptr() if resid is not None else None,
-                                        ptrs if len(grads) > 1 else None, len(grads), flag)
-            self._keep.append((kb, ptrs, grads, di, dv, resid))
+                                        ptrs if ptrs is not None and len(grads) > 1 else None, len(grads), flag)
+            self._keep.append((kb, ptrs, typed, grads, di, dv, resid, bucket))
 
 
 class Compressor:
@@ -213,33 +257,42 @@ class Compressor:
         return counts
 
     def merge_gather_compress_async(self, name: str, grads, k: int, dst_idx, dst_val, residual=None,
-                                    idx_offset: int = 0, count=None, stream=None):
+                                    idx_offset: int = 0, count=None, stream=None, bucket=None):
         """One MERGE task with the intra-node gather ahead of it
         (``stg_merge_gather_compress_device``; cpu_gather.cpp:59-87, then
         compress.cpp:139-186): ``grads[0] += residual + grads[1] + ... +
         grads[N-1]`` (this rank's slices, left to right), compress grads[0]
         under ``name``, and with ``residual`` its error feedback.  thresholdv16
-        sums the sources inside its streaming pass.  Returns the int32 count
+        sums the sources inside its streaming pass.  ``grads[1:]`` may be
+        float32, bfloat16 or float16; with ``bucket`` (float32: it receives the
+        sum and is what is compressed) ``grads[0]`` may be too and is only read
+        (``stg_merge_gather_compress_typed_device``).  Returns the int32 count
         tensor (no host sync)."""
         import torch
-        g0 = grads[0]
+        grads = list(grads)
+        f32 = [t for t in (residual, bucket) if t is not None]
+        g0 = grads[0] if bucket is None else bucket
         n = g0.numel()
-        for t in list(grads) + ([residual] if residual is not None else []) + [dst_idx, dst_val]:
+        for t in grads + f32 + [dst_idx, dst_val]:
             if not (t.is_cuda and t.is_contiguous()):
                 raise ValueError("merge_gather_compress: contiguous device tensors")
-        for t in list(grads) + ([residual] if residual is not None else []):
-            if t.numel() != n or t.dtype != torch.float32:
-                raise ValueError("merge_gather_compress: float32 sources of one size")
+        if any(t.numel() != n for t in grads + f32) or any(t.dtype != torch.float32 for t in f32) or \
+                any(grad_dtype(t) is None for t in grads):
+            raise ValueError("merge_gather_compress: float32 sources of one size")
+        typed = typed_sources("merge_gather_compress", grads, bucket)
         if count is None:
             count = torch.zeros(1, dtype=torch.int32, device=g0.device)
         kb = name.encode()
         b = StgBucket(kb, g0.data_ptr(), n, int(k), dst_idx.data_ptr(), dst_idx.numel(), dst_val.data_ptr(),
                       dst_val.numel(), int(idx_offset), count.data_ptr())
-        ptrs = (C.c_void_p * len(grads))(*[t.data_ptr() for t in grads])
         sp = stream if stream is not None else _stream_ptr(g0.device.index)
-        check(lib().stg_merge_gather_compress_device(
-            self._h, C.byref(b), C.c_void_p(residual.data_ptr()) if residual is not None else None, ptrs,
-            len(grads), C.c_void_p(sp)))
+        rp = C.c_void_p(residual.data_ptr()) if residual is not None else None
+        if typed is not None:
+            check(lib().stg_merge_gather_compress_typed_device(self._h, C.byref(b), rp, typed, len(grads),
+                                                               C.c_void_p(sp)))
+            return count
+        ptrs = (C.c_void_p * len(grads))(*[t.data_ptr() for t in grads])
+        check(lib().stg_merge_gather_compress_device(self._h, C.byref(b), rp, ptrs, len(grads), C.c_void_p(sp)))
         return count
 
     def merge_send_batch_async(self, items, stream=None, counts=None):
@@ -255,12 +308,18 @@ class Compressor:
         pairs.  ``dst_idx`` is int16 under flag 1 (else int32), ``dst_val``
         int16-typed fp16 bits under flag 2 (else float32); ``dst_idx.numel()``
         is the pair capacity.  Keys must be distinct within a call.
-        thresholdv16 only.  ``items`` may be a prebuilt ``SendTasks``.  Returns
+        thresholdv16 only.  ``items`` may be a prebuilt ``SendTasks``; an item
+        may carry bfloat16 / float16 gradients and a trailing ``bucket`` as
+        described there (``stg_merge_send_batch_typed_device``).  Returns
         the int32 counts tensor (no host sync)."""
         tasks = items if isinstance(items, SendTasks) else SendTasks(items, counts=counts)
         if not tasks.count:
             return tasks.counts
         sp = stream if stream is not None else _stream_ptr(tasks.device.index)
+        if tasks.srcs is not None:
+            check(lib().stg_merge_send_batch_typed_device(self._h, tasks.array, tasks.srcs, tasks.count,
+                                                          C.c_void_p(sp)))
+            return tasks.counts
         f = getattr(self, "_fn_send_cache", None)
         if f is None:
             f = self._fn_send_cache = lib().stg_merge_send_batch_device

@@ -697,6 +697,48 @@ stg::GatherArgs gather_args(float *dst, const float *resid, const float *const *
     return g;
 }
 
+// The same from typed sources (num_gpus in 1..16), checked: *why names what is
+// refused (STG_ERR_INVALID): an unknown dtype, a pointer not aligned to its
+// element, with n > 0 a null source at index >= 1 or a null array at
+// num_gpus > 1.  srcs[0] null, or fp32 and equal to dst, is the in-place first
+// term (src[0] stays null).  *typed: a launcher of the typed kernels is needed
+// (a 16-bit source or a first term read from srcs[0]); otherwise g is what
+// gather_args gives and the fp32 launchers take it.
+int typed_gather_args(float *dst, const float *resid, const stg_grad_src_t *srcs, int num_gpus, uint64_t n,
+                      stg::GatherArgs *g, bool *typed, std::string *why) {
+    *g = stg::GatherArgs{};
+    g->dst = dst;
+    g->resid = resid;
+    g->nsrc = (uint32_t)num_gpus;
+    *typed = false;
+    if (!srcs) {
+        if (num_gpus > 1 && n) { *why = "null srcs"; return STG_ERR_INVALID; }
+        g->nsrc = 1;
+        return STG_OK;
+    }
+    for (int i = 0; i < num_gpus; ++i) {
+        const stg_grad_src_t &x = srcs[i];
+        if (!x.d_grad) {
+            if (i == 0 || !n) continue;
+            *why = "null source";
+            return STG_ERR_INVALID;
+        }
+        if (x.dtype != STG_DT_F32 && x.dtype != STG_DT_BF16 && x.dtype != STG_DT_F16) {
+            *why = "unknown source dtype";
+            return STG_ERR_INVALID;
+        }
+        if (reinterpret_cast<uintptr_t>(x.d_grad) & (x.dtype == STG_DT_F32 ? 3u : 1u)) {
+            *why = "source not aligned to its element size";
+            return STG_ERR_INVALID;
+        }
+        if (i == 0 && x.dtype == STG_DT_F32 && x.d_grad == dst) continue;  // in place
+        g->src[i] = x.d_grad;
+        g->dtypes |= (uint32_t)x.dtype << (2 * i);
+        *typed |= i == 0 || x.dtype != STG_DT_F32;
+    }
+    return STG_OK;
+}
+
 // The table of one of ws.h's batched launchers on stream s (batch_pack.h): a
 // launch closes at the table's capacity or before its grid would pass `limit`.
 template <class Table>
@@ -925,14 +967,46 @@ int stg_merge_gather_compress_device(stg_codec_t h, const stg_bucket_t *bucket, 
                       b.d_count, s);
 }
 
+int stg_merge_gather_compress_typed_device(stg_codec_t h, const stg_bucket_t *bucket, float *d_residual,
+                                           const stg_grad_src_t *srcs, int num_gpus, void *stream) {
+    if (!h || !bucket) return fail(STG_ERR_INVALID, "null codec or bucket");
+    if (num_gpus < 1 || num_gpus > (int)stg::GATHER_MAX) return fail(STG_ERR_INVALID, "num_gpus must be in [1, 16]");
+    const stg_bucket_t &b = *bucket;
+    stg::GatherArgs g;
+    bool typed;
+    std::string why;
+    int rc = typed_gather_args(const_cast<float *>(b.d_src), d_residual, srcs, num_gpus, b.n, &g, &typed, &why);
+    if (rc) return fail(rc, why);
+    if (!typed) {  // fp32 in place: the fp32 entry point, its launchers and the in-scan gather
+        const float *f32[stg::GATHER_MAX] = {};
+        for (int i = 1; i < num_gpus; ++i) f32[i] = static_cast<const float *>(g.src[i]);
+        return stg_merge_gather_compress_device(h, bucket, d_residual, f32, num_gpus, stream);
+    }
+    if ((rc = validate(h, b.n, b.k, b.idx_cap, b.val_cap, b.d_count))) return rc;
+    if (b.n && !b.d_src) return fail(STG_ERR_INVALID, "null bucket buffer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(h->device));
+    // the typed gather-add pass, then the task as without a gather (thresholdv16: the plain scan)
+    HIP_TRY(stg::launch_gather_add_typed(g, 0, b.n, h->num_cu, s));
+    if (d_residual) return stg_merge_compress_batch_device(h, &b, &d_residual, 1, stream);
+    return run_device(h, b.key, b.d_src, b.d_src, b.n, b.k, b.d_idx, b.idx_cap, b.d_val, b.val_cap, b.idx_offset,
+                      b.d_count, s);
+}
+
 // the layout include/stg/codec.h documents (and stellatrain_amd/_capi.py mirrors)
+static_assert(sizeof(stg_grad_src_t) == 16 && offsetof(stg_grad_src_t, dtype) == 8, "stg_grad_src_t layout");
 static_assert(sizeof(stg_bucket_t) == 80 && offsetof(stg_bucket_t, d_count) == 72, "stg_bucket_t layout");
 static_assert(sizeof(stg_send_task_t) == 104 && offsetof(stg_send_task_t, d_residual) == 80 &&
                   offsetof(stg_send_task_t, d_grads) == 88 && offsetof(stg_send_task_t, num_gpus) == 96 &&
                   offsetof(stg_send_task_t, wire_flag) == 100,
               "stg_send_task_t layout");
 
-int stg_merge_send_batch_device(stg_codec_t h, const stg_send_task_t *tasks, size_t ntasks, void *stream) {
+// stg_merge_send_batch_device (srcs null) and stg_merge_send_batch_typed_device:
+// task i gathers from srcs[i] when srcs and srcs[i] are given, else from its
+// fp32 d_grads.  A call none of whose tasks has a 16-bit source or a typed first
+// term takes the fp32 launchers exactly as before.
+static int send_batch(stg_codec_t h, const stg_send_task_t *tasks, const stg_grad_src_t *const *srcs, size_t ntasks,
+                      void *stream) {
     CritPath crit_path;
     if (!h) return fail(STG_ERR_INVALID, "null codec handle");
     if (ntasks && !tasks) return fail(STG_ERR_INVALID, "null task array");
@@ -945,6 +1019,8 @@ int stg_merge_send_batch_device(stg_codec_t h, const stg_send_task_t *tasks, siz
     };
     std::unordered_map<std::string, size_t> seen;
     size_t live = 0, one = 0;  // tasks with n > 0; the last of them
+    std::vector<stg::GatherArgs> typed_g(srcs ? ntasks : 0);  // the gathers of the tasks with srcs[i]
+    bool any_typed = false;
     for (size_t i = 0; i < ntasks; ++i) {
         const stg_send_task_t &t = tasks[i];
         const stg_bucket_t &b = t.bucket;
@@ -953,11 +1029,22 @@ int stg_merge_send_batch_device(stg_codec_t h, const stg_send_task_t *tasks, siz
         if (t.wire_flag & ~3) return tfail(i, STG_ERR_INVALID, "unknown wire flag bits");
         if (t.num_gpus < 1 || t.num_gpus > (int)stg::GATHER_MAX)
             return tfail(i, STG_ERR_INVALID, "num_gpus must be in [1, 16]");
+        const stg_grad_src_t *ts = srcs ? srcs[i] : nullptr;
+        if (ts) {
+            bool typed;
+            std::string why;
+            const int rc = typed_gather_args(const_cast<float *>(b.d_src), t.d_residual, ts, t.num_gpus, b.n,
+                                             &typed_g[i], &typed, &why);
+            if (rc) return tfail(i, rc, why);
+            any_typed |= typed && b.n;
+        }
         if (b.n) {
             if (!b.d_src || (b.idx_cap && (!b.d_idx || !b.d_val))) return tfail(i, STG_ERR_INVALID, "null bucket buffer");
-            if (t.num_gpus > 1 && !t.d_grads) return tfail(i, STG_ERR_INVALID, "null d_grads");
-            for (int r = 1; r < t.num_gpus; ++r)
-                if (!t.d_grads[r]) return tfail(i, STG_ERR_INVALID, "null source");
+            if (!ts) {
+                if (t.num_gpus > 1 && !t.d_grads) return tfail(i, STG_ERR_INVALID, "null d_grads");
+                for (int r = 1; r < t.num_gpus; ++r)
+                    if (!t.d_grads[r]) return tfail(i, STG_ERR_INVALID, "null source");
+            }
             ++live;
             one = i;
         }
@@ -995,14 +1082,42 @@ int stg_merge_send_batch_device(stg_codec_t h, const stg_send_task_t *tasks, siz
     }
     auto gather_of = [&](size_t i) {
         const stg_send_task_t &t = tasks[i];
+        if (srcs && srcs[i]) return typed_g[i];
         return gather_args(const_cast<float *>(t.bucket.d_src), t.d_residual, t.d_grads, t.num_gpus);
     };
     // One task of 16-64 MiB alone: the one-bucket scan sums the sources in its
     // own streaming pass (tv16lone.hip), one pass over the bucket instead of two.
+    // That pass reads fp32 sources only: with a 16-bit source or a typed first
+    // term the typed gather-add runs first, then the plain scan (the same bits).
     const bool lone = live == 1 && tasks[one].bucket.n >= (size_t(1) << 22) && tasks[one].bucket.n <= (size_t(1) << 24);
-    if (lone) {
+    if (lone && any_typed) {
+        HIP_TRY(stg::launch_gather_add_typed(gather_of(one), 0, tasks[one].bucket.n, h->num_cu, s));
+        if ((rc = run_tv16(h, bk.data(), ntasks, s, res.data()))) return rc;
+    } else if (lone) {
         const stg::GatherArgs g = gather_of(one);
         if ((rc = run_tv16(h, bk.data(), ntasks, s, res.data(), &g, nullptr, one))) return rc;
+    } else if (any_typed) {
+        // the typed table for the whole call (an fp32 task is type 0 throughout): as many launches as below
+        auto gb = stream_packer<stg::SendGatherBatch>((uint64_t)h->num_cu * 8, stg::launch_gather_add_batch_typed, s);
+        for (size_t i = 0; i < ntasks; ++i) {
+            const size_t n = tasks[i].bucket.n;
+            if (!n) continue;
+            const stg::GatherArgs g = gather_of(i);
+            if (!g.resid && g.nsrc <= 1 && !g.src[0]) continue;  // (no term to add)
+            const stg::GatherPlan p = stg::gather_plan_of(g, 0, n);
+            stg::SendGather *d;
+            if ((rc = gb.add(stg::send_gather_blocks(n, p), &d))) return rc;
+            d->dst = g.dst;
+            d->resid = g.resid;
+            for (uint32_t r = 0; r < g.nsrc; ++r) d->src[r] = g.src[r];
+            d->n = n;
+            d->nsrc = g.nsrc;
+            d->vec = p.width;
+            d->head = p.head;
+            d->dtypes = g.dtypes;
+        }
+        if ((rc = gb.flush())) return rc;
+        if ((rc = run_tv16(h, bk.data(), ntasks, s, res.data()))) return rc;
     } else {
         // gather groups: a launch closes at SEND_BATCH tasks or before its grid
         // would pass num_cu * 8 workgroups (a larger tensor runs alone)
@@ -1012,7 +1127,7 @@ int stg_merge_send_batch_device(stg_codec_t h, const stg_send_task_t *tasks, siz
             const size_t n = t.bucket.n;
             if (!n || (!t.d_residual && t.num_gpus <= 1)) continue;  // (no term to add)
             const stg::GatherArgs g = gather_of(i);
-            auto phase = [](const float *p) { return reinterpret_cast<uintptr_t>(p) & 15u; };
+            auto phase = [](const void *p) { return reinterpret_cast<uintptr_t>(p) & 15u; };
             const uintptr_t ph = phase(g.dst);
             bool vec = (ph & 3u) == 0;
             if (g.resid) vec &= phase(g.resid) == ph;
@@ -1056,6 +1171,15 @@ int stg_merge_send_batch_device(stg_codec_t h, const stg_send_task_t *tasks, siz
         d->zero0 = b.idx_cap > count;
     }
     return fb.flush();
+}
+
+int stg_merge_send_batch_device(stg_codec_t h, const stg_send_task_t *tasks, size_t ntasks, void *stream) {
+    return send_batch(h, tasks, nullptr, ntasks, stream);
+}
+
+int stg_merge_send_batch_typed_device(stg_codec_t h, const stg_send_task_t *tasks,
+                                      const stg_grad_src_t *const *srcs, size_t ntasks, void *stream) {
+    return send_batch(h, tasks, srcs, ntasks, stream);
 }
 
 int stg_codec_compress_host(stg_codec_t h, const char *key, const float *src, size_t n, uint32_t k,
@@ -2037,6 +2161,43 @@ int stg_gather_add_device(float *d_grad0, const float *d_residual, const float *
     int ncu;
     if (const int rc = device_cus(&ncu)) return rc;
     HIP_TRY(stg::launch_gather_add(g, a, b, ncu, static_cast<hipStream_t>(stream)));
+    return STG_OK;
+}
+
+int stg_gather_add_typed_device(float *d_grad0, const float *d_residual, const stg_grad_src_t *srcs, int num_gpus,
+                                uint64_t n, int local_rank, void *stream) {
+    if (num_gpus < 1 || num_gpus > (int)stg::GATHER_MAX) return fail(STG_ERR_UNSUPPORTED, "num_gpus outside 1..16");
+    uint64_t a = 0, b = 0;
+    int rc = stg_gather_slice(n, local_rank, num_gpus, &a, &b);
+    if (rc) return rc;
+    stg::GatherArgs g;
+    bool typed;
+    std::string why;
+    if ((rc = typed_gather_args(d_grad0, d_residual, srcs, num_gpus, b - a, &g, &typed, &why))) return fail(rc, why);
+    if (a == b) return STG_OK;
+    if (!d_grad0) return fail(STG_ERR_INVALID, "null argument");
+    int ncu;
+    if (const int rc = device_cus(&ncu)) return rc;
+    // fp32 in place: the fp32 launcher (g is then what gather_args builds)
+    HIP_TRY((typed ? stg::launch_gather_add_typed : stg::launch_gather_add)(g, a, b, ncu, static_cast<hipStream_t>(stream)));
+    return STG_OK;
+}
+
+int stg_debug_gather_plan(const uint64_t *addrs, const int *dtypes, size_t nstreams, uint64_t n, uint32_t *width,
+                          uint32_t *head) {
+    if (!addrs || !dtypes || !width || !head || nstreams < 1 || nstreams > stg::GATHER_MAX + 2)
+        return fail(STG_ERR_INVALID, "null argument or stream count outside 1..18");
+    uintptr_t addr[stg::GATHER_MAX + 2];
+    uint32_t esz[stg::GATHER_MAX + 2];
+    for (size_t i = 0; i < nstreams; ++i) {
+        if (dtypes[i] != STG_DT_F32 && dtypes[i] != STG_DT_BF16 && dtypes[i] != STG_DT_F16)
+            return fail(STG_ERR_INVALID, "unknown dtype");
+        addr[i] = (uintptr_t)addrs[i];
+        esz[i] = dtypes[i] == STG_DT_F32 ? 4u : 2u;
+    }
+    const stg::GatherPlan p = stg::gather_plan(addr, esz, (uint32_t)nstreams, n, stg::gather_max_width());
+    *width = p.width;
+    *head = p.head;
     return STG_OK;
 }
 

@@ -18,11 +18,15 @@
 //
 // Bounds.  gather_add_batch: HBM (xGMI for peer sources), 4 (dst) + 4
 // (residual) + 4 (N - 1) + 4 (store) bytes per element, float4 lanes with
-// nontemporal source loads.  ef_pack_batch: k pairs per tensor (1 % of it),
-// one pair per lane, so the launch is latency-bound like wire_encode.
+// nontemporal source loads; gather_add_batch_typed reads bf16 / fp16 sources
+// as they are, 2 bytes per element each (lane groups of 8 or 4 elements), and
+// the first term from a typed source when the task has one.  ef_pack_batch: k
+// pairs per tensor (1 % of it), one pair per lane, so the launch is
+// latency-bound like wire_encode.
 #include <algorithm>
 
 #include "ws.h"
+#include "gather_dev.h"
 #include "wire_dev.h"
 
 namespace stg {
@@ -31,14 +35,9 @@ namespace {
 
 typedef float f4v __attribute__((ext_vector_type(4)));
 
-// gather.hip's per-element sum, in its order: dst, residual, grad[1], ...
-__device__ __forceinline__ void gather_one(const SendGather &a, size_t e) {
-    float acc = a.dst[e];
-    if (a.resid) acc += a.resid[e];
-    for (uint32_t s = 1; s < a.nsrc; ++s) acc += a.src[s][e];
-    a.dst[e] = acc;
-}
-
+// (the per-element sum is gather.hip's, in its order -- dst, residual,
+// grad[1], ... -- from gather_dev.h)
+//
 // A workgroup owns SEND_GATHER_TILE elements of its task.  Where every pointer
 // of the task shares one 16-byte phase (a.vec) the tile is four float4 per lane
 // counted from the first aligned element, every source's float4 loaded before
@@ -53,7 +52,7 @@ __global__ void __launch_bounds__(STG_WG) gather_add_batch(SendGatherBatch w) {
     if (!a.vec) {
         for (uint32_t u = 0; u < SEND_GATHER_TILE / STG_WG; ++u) {
             const size_t e = wb * SEND_GATHER_TILE + u * STG_WG + threadIdx.x;
-            if (e < a.n) gather_one(a, e);
+            if (e < a.n) gather_elem<false>(a, e);
         }
         return;
     }
@@ -67,7 +66,8 @@ __global__ void __launch_bounds__(STG_WG) gather_add_batch(SendGatherBatch w) {
         const f4v r = a.resid ? __builtin_nontemporal_load(reinterpret_cast<const f4v *>(a.resid + e)) : f4v{0, 0, 0, 0};
 #pragma unroll
         for (uint32_t s = 1; s < MAXS; ++s)
-            if (s < a.nsrc) x[s] = __builtin_nontemporal_load(reinterpret_cast<const f4v *>(a.src[s] + e));
+            if (s < a.nsrc)
+                x[s] = __builtin_nontemporal_load(reinterpret_cast<const f4v *>(static_cast<const float *>(a.src[s]) + e));
         if (a.resid) acc += r;
 #pragma unroll
         for (uint32_t s = 1; s < MAXS; ++s)
@@ -76,7 +76,42 @@ __global__ void __launch_bounds__(STG_WG) gather_add_batch(SendGatherBatch w) {
     }
     if (wb == 0) {
         const size_t vt = v0 + 4 * nv, ns = v0 + (a.n - vt);  // head + tail elements: at most 6
-        if (threadIdx.x < ns) gather_one(a, threadIdx.x < v0 ? threadIdx.x : vt + (threadIdx.x - v0));
+        if (threadIdx.x < ns) gather_elem<false>(a, threadIdx.x < v0 ? threadIdx.x : vt + (threadIdx.x - v0));
+    }
+}
+
+// The same for tables with a 16-bit source or a typed first term (a.dtypes,
+// a.src[0]; gather_dev.h): a.vec is the task's lane-group width W (ws.h
+// GatherPlan) -- the tile is SEND_GATHER_TILE / W groups counted from a.head,
+// head (< W) and tail (< W) scalar in the task's first workgroup -- or 0 for a
+// scalar tile.  The width is uniform over the workgroup.
+template <uint32_t MAXS, uint32_t W>
+__device__ __forceinline__ void gather_typed_tile(const SendGather &a, size_t wb) {
+    const size_t v0 = a.head, nv = (a.n - v0) / W;
+    for (uint32_t u = 0; u < SEND_GATHER_TILE / W / STG_WG; ++u) {
+        const size_t i = wb * (SEND_GATHER_TILE / W) + u * STG_WG + threadIdx.x;
+        if (i >= nv) break;
+        gather_lane<MAXS, W>(a, v0 + W * i);
+    }
+    if (wb == 0) {
+        const size_t vt = v0 + W * nv, ns = v0 + (a.n - vt);  // head + tail elements: at most 2 (W - 1)
+        if (threadIdx.x < ns) gather_elem<true>(a, threadIdx.x < v0 ? threadIdx.x : vt + (threadIdx.x - v0));
+    }
+}
+
+template <uint32_t MAXS>
+__global__ void __launch_bounds__(STG_WG) gather_add_batch_typed(SendGatherBatch w) {
+    const SendGather &a = w.t[batch_item(w.t, w.nt)];
+    const size_t wb = blockIdx.x - a.blk0;
+    if (a.vec == 8) {
+        gather_typed_tile<MAXS, 8>(a, wb);
+    } else if (a.vec == 4) {
+        gather_typed_tile<MAXS, 4>(a, wb);
+    } else {
+        for (uint32_t u = 0; u < SEND_GATHER_TILE / STG_WG; ++u) {
+            const size_t e = wb * SEND_GATHER_TILE + u * STG_WG + threadIdx.x;
+            if (e < a.n) gather_elem<true>(a, e);
+        }
     }
 }
 
@@ -147,6 +182,16 @@ hipError_t launch_gather_add_batch(const SendGatherBatch &w, uint32_t blocks, hi
     if (maxs <= 4) gather_add_batch<4><<<blocks, STG_WG, 0, s>>>(w);
     else if (maxs <= 8) gather_add_batch<8><<<blocks, STG_WG, 0, s>>>(w);
     else gather_add_batch<GATHER_MAX><<<blocks, STG_WG, 0, s>>>(w);
+    return hipGetLastError();
+}
+
+hipError_t launch_gather_add_batch_typed(const SendGatherBatch &w, uint32_t blocks, hipStream_t s) {
+    if (!w.nt || !blocks) return hipSuccess;
+    uint32_t maxs = 1;
+    for (uint32_t i = 0; i < w.nt; ++i) maxs = std::max(maxs, w.t[i].nsrc);
+    if (maxs <= 4) gather_add_batch_typed<4><<<blocks, STG_WG, 0, s>>>(w);
+    else if (maxs <= 8) gather_add_batch_typed<8><<<blocks, STG_WG, 0, s>>>(w);
+    else gather_add_batch_typed<GATHER_MAX><<<blocks, STG_WG, 0, s>>>(w);
     return hipGetLastError();
 }
 

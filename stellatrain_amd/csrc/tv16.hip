@@ -875,7 +875,7 @@ hipError_t launch_lone(const Tv16Launch &a, const DevWS &ws, const BatchArgs &A,
     if (fused_gather) {  // (bucket 0's gather has a term to add)
         const GatherArgs &g = *b.gather;
         L.gres = g.resid;
-        for (uint32_t x = 1; x < g.nsrc && x < GATHER_MAX; ++x) L.gsrc[x] = g.src[x];
+        for (uint32_t x = 1; x < g.nsrc && x < GATHER_MAX; ++x) L.gsrc[x] = static_cast<const float *>(g.src[x]);
         L.gn = std::max<uint32_t>(1, g.nsrc);
     }
     hipError_t e = launch_tv16_lscan(L, a.num_cu, s);  // (clamps L.fin to what the grid allows)

@@ -180,9 +180,38 @@ constexpr uint32_t GATHER_MAX = 16;  // local GPUs per node the gather-add accep
 struct GatherArgs {
     float *dst;                    // grad[0]
     const float *resid;            // residual (or null: no residual term)
-    const float *src[GATHER_MAX];  // src[1 .. nsrc-1] = grad[1 .. N-1]; src[0] unused
+    const void *src[GATHER_MAX];   // src[1 .. nsrc-1] = grad[1 .. N-1].  src[0]: the typed launchers' first term
+                                   // when not null (dst is then write-only); the fp32 launchers ignore it
     uint32_t nsrc;                 // N, the node's GPU count
+    uint32_t dtypes;               // typed launchers: src[s]'s STG_DT_* type in bits 2 s, 2 s + 1 (one scalar
+                                   // word, as PublishTask::dtypes); the fp32 launchers read every source as float
 };
+// How a typed gather-add runs over n elements: `head` scalar elements, then
+// lane groups of `width` elements (8: one 16-byte load per 16-bit stream and
+// two per fp32 stream; 4: 8 and 16 bytes), then a scalar tail < width.  A
+// stream is dst, the residual or a source, taken at the first element of the
+// range: addr[i] its byte address there, esz[i] its element size (4 or 2).
+// The 8-wide group runs when one head < 8 brings every fp32 stream to 16 bytes
+// and every 16-bit stream to 16 bytes; else the 4-wide one when one head < 4
+// brings them to 16 and 8 bytes; else width 0, every element scalar (head 0).
+// head <= n always (a range shorter than its head is all head).
+struct GatherPlan {
+    uint32_t width, head;
+};
+inline GatherPlan gather_plan(const uintptr_t *addr, const uint32_t *esz, uint32_t ns, uint64_t n, uint32_t max_width = 8) {
+    for (uint32_t w = 8; w >= 4; w >>= 1) {
+        if (w > max_width) continue;
+        for (uint32_t h = 0; h < w; ++h) {
+            bool ok = true;
+            for (uint32_t i = 0; i < ns && ok; ++i)
+                ok = ((addr[i] + (uintptr_t)esz[i] * h) & (esz[i] == 4 ? 15u : 2u * w - 1u)) == 0;
+            if (ok) return GatherPlan{w, (uint32_t)(h < n ? h : n)};
+        }
+    }
+    return GatherPlan{0, 0};
+}
+// the plan of a's streams over [start, end), as launch_gather_add_typed takes it
+GatherPlan gather_plan_of(const GatherArgs &a, size_t start, size_t end);
 struct Tv16Bucket {
     const float *src;
     size_t n;
@@ -550,6 +579,9 @@ hipError_t launch_merge_world_scatter(const MergeScatterArgs &w, uint32_t blocks
 hipError_t launch_merge_world_emit(const MergeWorldArgs &w, uint32_t blocks, int opt, hipStream_t s,
                                    uint64_t *launches = nullptr);
 hipError_t launch_gather_add(const GatherArgs &a, size_t start, size_t end, int num_cu, hipStream_t s);
+// ... with 16-bit sources and / or a first term read from src[0] (gather.hip)
+hipError_t launch_gather_add_typed(const GatherArgs &a, size_t start, size_t end, int num_cu, hipStream_t s);
+uint32_t gather_max_width();  // 8; STG_DEBUG_GATHER_WIDTH=4 keeps the typed launchers to 4-wide groups (measurements)
 constexpr uint32_t WIRE_BATCH = 16;  // buckets per batched wire launch
 struct WireBucket {
     const uint32_t *idx;
@@ -572,12 +604,14 @@ constexpr uint32_t SEND_GATHER_TILE = STG_WG * 16;    // elements per gather wor
 struct SendGather {
     float *dst;                    // grad[0]
     const float *resid;            // residual term (or null)
-    const float *src[GATHER_MAX];  // src[1 .. nsrc-1] = grad[1 .. N-1]; src[0] unused
+    const void *src[GATHER_MAX];   // src[1 .. nsrc-1] = grad[1 .. N-1]; src[0] as GatherArgs::src[0]
     uint64_t n;
     uint32_t nsrc;                 // N
     uint32_t blk0;                 // first workgroup of this tensor in the launch
-    uint32_t vec;                  // every pointer shares one 16-byte phase: float4 body
-    uint32_t head;                 // vec: elements before the first 16-byte aligned one (< 4, <= n)
+    uint32_t vec;                  // fp32 launch: every pointer shares one 16-byte phase (float4 body);
+                                   // typed launch: GatherPlan::width (0: scalar tiles)
+    uint32_t head;                 // vec: elements before the first lane group (< 4; typed: < 8; <= n)
+    uint32_t dtypes;               // as GatherArgs::dtypes (typed launch)
 };
 struct SendGatherBatch {
     SendGather t[SEND_BATCH];
@@ -585,6 +619,14 @@ struct SendGatherBatch {
 };
 static_assert(sizeof(SendGatherBatch) <= 3072, "kernel arguments: stay under 4 KiB");
 hipError_t launch_gather_add_batch(const SendGatherBatch &w, uint32_t blocks, hipStream_t s);
+// the same launch for tables with a 16-bit source or a typed first term (vec = the plan's width)
+hipError_t launch_gather_add_batch_typed(const SendGatherBatch &w, uint32_t blocks, hipStream_t s);
+// workgroups of a typed task of n elements under plan p
+inline uint64_t send_gather_blocks(uint64_t n, GatherPlan p) {
+    const uint64_t per = p.width ? SEND_GATHER_TILE / p.width : SEND_GATHER_TILE;
+    const uint64_t units = p.width ? (n - p.head) / p.width : n;
+    return units ? (units + per - 1) / per : 1;
+}
 struct SendFinish {
     const uint32_t *idx;           // the scan's staged pairs: true indices (+ idx_offset) ...
     const float *val;              // ... and values, `count` of each

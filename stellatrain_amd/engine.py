@@ -22,7 +22,7 @@ import numpy as np
 
 from ._capi import (STG_DT_BF16, STG_DT_F16, STG_DT_F32, CodecError, StgMergeTask, StgPublishTask, StgRankStream,
                     StgReplica, StgWireRx, check, lib)
-from .compressor import Compressor, make_compressor
+from .compressor import Compressor, make_compressor, typed_sources
 
 __all__ = ["CodecEngine", "SparseSGD", "MergeTasks", "merge_numel", "api_numel", "scatter_merge", "scatter_merge_wire",
            "wire_decode_batch", "owner_of", "merge_batch_launches", "PublishTasks", "publish_params"]
@@ -139,13 +139,18 @@ class CodecEngine:
         and the wire form ``wire_flag(n, fp16_values)``.  Returns ``(streams,
         counts)``: per item ``(idx, val, flag)`` with ``numel * world`` zeroed
         slots in the flag's types, the first ``numel`` this node's stream in the
-        form the ring sends, and the int32 counts tensor (no host sync)."""
+        form the ring sends, and the int32 counts tensor (no host sync).  An
+        item may be ``(key, grads, residual, bucket)``: ``grads`` of float32,
+        bfloat16 or float16 and ``bucket`` the float32 tensor that receives the
+        sum, as ``SendTasks`` describes (without ``bucket``, ``grads[1:]`` may
+        still be 16-bit)."""
         import torch
         send, streams = [], []
         for it in items:
             key, grads = it[0], list(it[1])
             residual = it[2] if len(it) > 2 else None
-            if not all(t.is_contiguous() for t in grads + ([residual] if residual is not None else [])):
+            bucket = it[3] if len(it) > 3 else None
+            if not all(t.is_contiguous() for t in grads + [t for t in (residual, bucket) if t is not None]):
                 raise ValueError("send_buckets: gradients and residual must be contiguous")
             n = grads[0].numel()
             numel = merge_numel(n, self.compression_ratio_, world)
@@ -154,7 +159,8 @@ class CodecEngine:
             idx = torch.zeros(numel * world, dtype=di, device=grads[0].device)
             val = torch.zeros(numel * world, dtype=dv, device=grads[0].device)
             send.append((key, [g.reshape(-1) for g in grads], numel, idx[:numel], val[:numel],
-                         residual.reshape(-1) if residual is not None else None, flag))
+                         residual.reshape(-1) if residual is not None else None, flag) +
+                        ((0, bucket.reshape(-1)) if bucket is not None else ()))
             streams.append((idx, val, flag))
         counts = self.compressor_.merge_send_batch_async(send)
         return streams, counts
@@ -227,14 +233,34 @@ def gather_slice(n: int, local_rank: int, num_gpus: int):
     return a.value, b.value
 
 
-def gather_add(grads, residual, local_rank: int) -> None:
+def gather_add(grads, residual, local_rank: int, out=None) -> None:
     """ModuleCpuGather::run on the device (cpu_gather.cpp:59-87): over this
     local rank's slice, ``grads[0] += residual + grads[1] + ... + grads[N-1]``
     left to right, in one pass.  ``grads`` are float32 device tensors of one
-    size (peers' buffers where P2P is enabled); ``residual`` may be None."""
+    size (peers' buffers where P2P is enabled); ``residual`` may be None.
+    ``grads[1:]`` may also be bfloat16 or float16 (16-bit model replicas'
+    gradients): they are widened, exactly, as they are loaded
+    (``stg_gather_add_typed_device``).  With ``out``, a float32 tensor, the
+    slice of ``out`` receives the sum and ``grads[0]``, of any of the three
+    types, is only read; a 16-bit ``grads[0]`` without ``out`` is a
+    ValueError."""
     import torch
     g0 = grads[0]
     n = g0.numel()
+    if out is not None or any(t.dtype in (torch.bfloat16, torch.float16) for t in grads):
+        f32 = [t for t in (residual, out) if t is not None]
+        typed = typed_sources("gather_add", grads, out)
+        if any(t.dtype != torch.float32 for t in f32):
+            raise ValueError("gather_add: float32 residual and out")
+        for t in list(grads) + f32:
+            if t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError("gather_add: contiguous device tensors of one size")
+        d0 = g0 if out is None else out
+        check(lib().stg_gather_add_typed_device(C.c_void_p(d0.data_ptr()),
+                                                C.c_void_p(residual.data_ptr()) if residual is not None else None,
+                                                typed, len(grads), n, local_rank,
+                                                C.c_void_p(torch.cuda.current_stream(d0.device.index).cuda_stream)))
+        return
     for t in list(grads) + ([residual] if residual is not None else []):
         if t.numel() != n or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
             raise ValueError("gather_add: contiguous float32 device tensors of one size")

@@ -473,6 +473,87 @@ def gather(torch, calls):
     return out
 
 
+def gather16(torch, calls):
+    """The gather-add of a 64 MiB bucket whose N - 1 peers are bf16 (16-bit
+    model replicas' gradients): gather_add on the bf16 tensors as they are
+    against what it took before -- a torch cast of every peer into an fp32
+    temporary, then the fp32 gather_add -- in the same run.  Bytes per element:
+    12 + 2 (N - 1) against 12 + 10 (N - 1)."""
+    import os
+    from stellatrain_amd import gather_add
+    from stellatrain_amd._capi import lib
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev)
+    n = 16 << 20
+    out = []
+    for g in (2, 4, 8):
+        srcs = bufs_for(torch, lib(), dev, n, g + 1, st.cuda_stream, 600)
+        bucket, resid = srcs[0], srcs[g]
+        peers = [s.to(torch.bfloat16) for s in srcs[1:g]]
+        tmp = srcs[1:g]  # the fp32 temporaries of the cast
+
+        def typed(s):
+            for r in range(g):
+                gather_add([bucket] + peers, resid, r)
+
+        def cast(s):
+            for t, p in zip(tmp, peers):
+                t.copy_(p)
+            for r in range(g):
+                gather_add([bucket] + tmp, resid, r)
+        us16, us32 = _time_loop(torch, st, typed, calls, 2), _time_loop(torch, st, cast, calls, 2)
+        model = (12.0 + 2 * (g - 1)) / (12.0 + 10 * (g - 1))
+        out.append({"config": f"GATHER-ADD 64 MiB bucket, N={g}: bf16 peers + residual",
+                    "typed_us": round(us16, 2), "cast_then_fp32_us": round(us32, 2), "ratio": round(us16 / us32, 3),
+                    "byte_model_ratio": round(model, 3), "alg_GBps": round((12.0 + 2 * (g - 1)) * n / us16 / 1e3, 1),
+                    "lane_group": int(os.environ.get("STG_DEBUG_GATHER_WIDTH", "8"))})
+        del srcs, bucket, resid, peers, tmp
+    return out
+
+
+def send16(torch, calls):
+    """The one-call send path on 256 tensors of 60,000 floats, N = 2 with a bf16
+    peer: merge_send_batch_async on the bf16 tensors (a prebuilt SendTasks)
+    against a torch cast of every 16-bit tensor to fp32 and the fp32 call, in
+    the same run; once with the bucket as the first term, once with a bf16
+    local gradient as a typed first term (the cast path widens it into the
+    bucket first)."""
+    from stellatrain_amd import SendTasks, ThresholdvCompressor16
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev)
+    nt, n, k = 256, 60000, 600
+    out = []
+    for term0 in (False, True):
+        gen = torch.Generator(device=dev).manual_seed(16)
+        mk = lambda: torch.randn(nt, n, device=dev, generator=gen) * 1e-3  # noqa: E731
+        bucket, resid, peer32, idx, val = mk(), mk() * 0.25, mk(), torch.zeros(nt, k, dtype=torch.int16, device=dev), \
+            torch.zeros(nt, k, dtype=torch.float32, device=dev)
+        local16, peer16 = mk().to(torch.bfloat16), peer32.to(torch.bfloat16)
+        row = {"config": f"SEND path, 256 x 60,000 floats, N=2 bf16 peer, k={k}"
+                         + (", bf16 local gradient as typed first term" if term0 else "")}
+        for typed in (True, False):
+            comp = ThresholdvCompressor16()
+            if typed:
+                items = [(f"s{j}@w", [local16[j] if term0 else bucket[j], peer16[j]], k, idx[j], val[j], resid[j], 1)
+                         + ((0, bucket[j]) if term0 else ()) for j in range(nt)]
+            else:
+                items = [(f"s{j}@w", [bucket[j], peer32[j]], k, idx[j], val[j], resid[j], 1) for j in range(nt)]
+            tasks = SendTasks(items)
+
+            def step(s):
+                if not typed:  # one cast launch per tensor and source, as a per-tensor engine would issue them
+                    for j in range(nt):
+                        peer32[j].copy_(peer16[j])
+                        if term0:
+                            bucket[j].copy_(local16[j])
+                comp.merge_send_batch_async(tasks)
+            us = _time_loop(torch, st, step, max(4, calls // 4), 3)
+            row["typed_us" if typed else "cast_then_fp32_us"] = round(us, 1)
+        row["ratio"] = round(row["typed_us"] / row["cast_then_fp32_us"], 3)
+        out.append(row)
+    return out
+
+
 def gather_fused(torch, calls):
     """One MERGE task with the intra-node gather ahead of it on a 64 MiB
     bucket (cpu_gather.cpp:59-87 then compress.cpp:139-186):
@@ -807,6 +888,12 @@ def main():
             emit(r)
     if "gather" in only:
         for d in gather(torch, a.calls):
+            emit(d)
+    if "gather16" in only:
+        for d in gather16(torch, a.calls):
+            emit(d)
+    if "send16" in only:
+        for d in send16(torch, a.calls):
             emit(d)
     if "ef" in only:
         for d in merge_ef(torch, max(8, a.calls // 4)):
