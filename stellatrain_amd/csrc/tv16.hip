@@ -210,9 +210,7 @@ struct Ctx {
     }
 };
 
-constexpr uint32_t TAG_AGG = 1, TAG_DEC = TV16_TAG_DEC;
-constexpr uint32_t DEC_B = TV16_DEC_B, DEC_WIN = TV16_DEC_WIN, DEC_TAIL = TV16_DEC_TAIL;
-constexpr uint32_t WIN = TV16_WIN;
+constexpr uint32_t TAG_AGG = 1;
 
 // ===========================================================================
 // streaming waves
@@ -243,7 +241,7 @@ __device__ __forceinline__ void scan_chunk(Ctx &C, uint32_t j, uint32_t k, uint3
     const uint32_t lane = flane(), q = lane & 3;
     if (s == 0 && lane == 0) { L.tval[par] = t; L.incv[par] = uni(d.state->inc); }
     const uint32_t tb = f2u(t);
-    const uint32_t wlo = tb > WIN ? tb - WIN : 0u;  // window [wlo, tb) just below t
+    const uint32_t wlo = window_lo(tb);  // window [wlo, tb) just below t
     const uint32_t steps = (nl + 15) / 16;          // 16 lines per wave step
     const uint32_t mine = steps > s ? (steps - s + NS - 1) / NS : 0u;
     uint32_t cnt_w = 0, win_w = 0;
@@ -476,8 +474,9 @@ __device__ __forceinline__ void finish_chunk(Ctx &C, uint32_t j, uint32_t k) {
     const uint32_t ww = uni(L.wcnt[par]);
 
     // ---- ordered emission of the chunk's qualifying lines with rank < lim ----
-    const uint32_t kb = d.dst_len / 16, r = d.dst_len % 16;
-    const uint32_t lim = kb + (r ? 1u : 0u);
+    Regime R;
+    regime_lines(R, d.dst_len);
+    const uint32_t kb = R.kb, r = R.r, lim = R.lim;
     const bool vec = aligned16(d);
     if (P < lim && qw) {
         if (qw <= STAGE_B) {
@@ -553,7 +552,7 @@ __device__ __forceinline__ void finish_chunk(Ctx &C, uint32_t j, uint32_t k) {
             // an LDS list overflowed: list the window from src, in order,
             // counting the qualifying lines before each (as the scan decides:
             // qualifying S >= t, window wlo <= bits(S) < bits(t))
-            const uint32_t wlo = tb > WIN ? tb - WIN : 0u;
+            const uint32_t wlo = window_lo(tb);
             uint32_t base = Wbef, qb = P;
             for (uint32_t i0 = 0; i0 < nl; i0 += 64) {
                 const uint32_t i = i0 + lane;
@@ -578,20 +577,16 @@ __device__ __forceinline__ void finish_chunk(Ctx &C, uint32_t j, uint32_t k) {
     // ---- the bucket's last chunk: regime, tail, AIMD, count, decision ----
     if (c + 1 == d.nc) {
         const uint32_t Qtot = P + qw, Wtot = Wbef + ww;
-        const uint32_t c0 = Qtot >= lim ? d.dst_len : 16u * Qtot;
-        bool tail_cand = false;
-        float tail_key = 0.f;
-        uint32_t ct = 0;
-        if (c0 < d.dst_len && d.tl) {  // stage 3: the ragged tail's signed, sequential sum
+        regime_head(R, d.dst_len, Qtot);
+        regime_no_tail(R);
+        if (regime_sums_tail(R, d.dst_len, d.tl)) {  // stage 3: the ragged tail's signed, sequential sum
             const float *tp = d.src + (size_t)d.nb * 16;
             float s = 0.f;
             for (uint32_t i = 0; i < d.tl; ++i) s += tp[i];
-            s = uni(s);
-            if (s * 16.0f >= t * (float)d.tl) ct = std::min(d.dst_len - c0, d.tl);
-            else { tail_cand = true; tail_key = s * 16.0f / (float)d.tl; }
+            regime_tail(R, uni(s), t, d.tl, d.dst_len);
         }
-        const uint32_t cnt = c0 + ct;
-        const bool regimeB = cnt < d.dst_len;
+        const uint32_t c0 = R.c0, ct = R.ct;
+        const bool regimeB = regime_short(R, d.dst_len);
         if (lane == 0) {
             if (ct) {
                 const size_t p0 = (size_t)d.nb * 16;
@@ -599,25 +594,23 @@ __device__ __forceinline__ void finish_chunk(Ctx &C, uint32_t j, uint32_t k) {
                     put_pair(d, c0 + i, (uint32_t)(p0 + i) + (uint32_t)d.idx_offset, d.src[p0 + i]);
                 }
             }
-            d.state->t = regimeB ? (float)((double)t * 0.99) : t + inc;
+            d.state->t = next_threshold(t, inc, regimeB);
             d.state->inc = inc;
             d.state->init = 1;
-            st_sc1(d.count_out, (uint32_t)std::min<uint64_t>(d.dst_len, (uint64_t)d.nb * 16 + d.tl));
+            st_sc1(d.count_out, emitted_count(d.dst_len, d.nb, d.tl));
             // a bounded wait anywhere in the launch gave up: the output is untrusted
             if (ld_sc1(C.failp)) st_sc1(d.count_out, POISON_COUNT);
         }
-        const uint32_t ncand = d.nb - Qtot;  // non-qualifying full lines
-        const uint32_t M = regimeB ? std::min((d.dst_len - cnt + 15u) / 16u, ncand) : 0u;
-        uint32_t flags = 0;
-        if (regimeB) flags = DEC_B | (tail_cand ? DEC_TAIL : 0u) | (Wtot >= M && Wtot + 1 <= CAND_CAP ? DEC_WIN : 0u);
+        regime_close(R, d.dst_len, d.nb, Qtot, Wtot);  // (after the state's stores: ahead of them it costs a VGPR)
+        const DecisionWords dw = decision_pack(R, Wtot, Qtot, t, decision_tag(C.A.epoch));
         Decision &D = C.ctl()->dec[b];
         if (lane == 0) {
-            st_sc1(&D.w[1], ((uint64_t)cnt << 32) | M);
-            st_sc1(&D.w[2], ((uint64_t)Wtot << 32) | __float_as_uint(tail_key));
-            st_sc1(&D.w[3], ((uint64_t)Qtot << 32) | __float_as_uint(t));
+            st_sc1(&D.w[1], dw.w[1]);
+            st_sc1(&D.w[2], dw.w[2]);
+            st_sc1(&D.w[3], dw.w[3]);
         }
         vm_drain();
-        if (lane == 0) st_sc1(&D.w[0], ((uint64_t)C.tag(TAG_DEC) << 32) | flags);
+        if (lane == 0) st_sc1(&D.w[0], dw.w[0]);
     }
 }
 

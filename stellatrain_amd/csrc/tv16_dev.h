@@ -1,9 +1,13 @@
-// tv16_dev.h -- device helpers shared by the thresholdv16 scan (tv16.hip) and
-// its regime-B heap fill (tv16fill.hip).  gfx950 only.
+// tv16_dev.h -- device helpers shared by the thresholdv16 launches: the batched
+// scan (tv16.hip), the one-bucket scan (tv16lone.hip) and the regime-B heap
+// fill (tv16fill.hip), with the headers these include.  gfx950 only.  The
+// scalar rules the finishes share (regime, Decision words, window, pops, heap
+// keys) are in tv16_finish.h, which a host compiler takes too.
 #pragma once
 
 #include <algorithm>
 
+#include "tv16_finish.h"
 #include "ws.h"
 #include "wire_dev.h"
 
@@ -98,21 +102,6 @@ __device__ __forceinline__ void gather16(const void *src, uint32_t n16, void *ds
                                          reinterpret_cast<char *>(dst) + c * 1024, 16, 0, 16 /* sc1 */);
     }
     vm_drain();
-}
-
-// Heap positions of libstdc++'s make_heap (node q = pos + 1 >= 1).
-__device__ __forceinline__ uint32_t depth_of(uint32_t q) { return 31u - __clz(q); }
-// right-first pre-order key of heap position pos (< 2^20 - 1): ancestors
-// first, then the right subtree before the left one
-__device__ __forceinline__ uint32_t rf_key(uint32_t pos) {
-    const uint32_t q = pos + 1, d = depth_of(q);
-    const uint32_t path = q - (1u << d);
-    const uint32_t inv = ~path & ((1u << d) - 1u);
-    return ((inv << (19u - d)) << 5) | d;
-}
-__device__ __forceinline__ bool is_desc(uint32_t q, uint32_t qt) {  // heap node q (pos + 1) below node qt
-    const uint32_t dp = depth_of(q), dt = depth_of(qt);
-    return dp > dt && (q >> (dp - dt)) == qt;
 }
 
 }  // namespace tv16

@@ -69,7 +69,6 @@ constexpr uint32_t FILL_WG = 512;              // 8 waves: beside two 12-wave sc
 constexpr uint32_t FNW_F = FILL_WG / 64;
 constexpr uint32_t EMAX = 4096;                // window entries kept (+ the ragged tail)
 constexpr uint32_t VCAP = 6144;                // shadow-heap nodes held (more: full path)
-constexpr uint32_t POS_LIM = (1u << 20) - 1;   // fast path: N <= POS_LIM (20-bit paths)
 constexpr uint32_t NONE = 0xffffffffu;
 constexpr uint32_t NONE13 = 0x1fffu;           // no node (13-bit node index)
 constexpr uint32_t CNONE = 0xffffffu;          // content -inf (24-bit content field)
@@ -217,6 +216,8 @@ __device__ __forceinline__ void emit_order_w(const Tv16FillBucket &d, uint32_t c
     constexpr uint32_t LPR = FILL_WG / 4;  // lines per round; K rounds of loads in flight
     const bool vec = aligned16(d) && (cnt & 3u) == 0;
     const uint32_t q = threadIdx.x & 3u;
+    // (pop_offset / pop_len of tv16_finish.h written out: through the helpers tv16_fill<false> goes from 8 to
+    // 10 VGPR spills and the other three fill kernels lose 22 to 91 SGPR spills)
     auto span = [&](uint32_t i, uint32_t &off, uint32_t &len) {  // output offset and length of entry i
         len = 0;
         off = 16u * i - (tail_rank < i ? 16u - d.tl : 0u);
@@ -628,9 +629,9 @@ tv16_fill(Tv16FillArgs A) {
         // how the call's fill was ordered (debug words 48..51: rankers without
         // ties, rankers with ties, the orderer after a violation, the orderer
         // for a call the rankers could not take; tests read them)
-        const bool ranked = A.rankers && !(rep & LF_FALLBACK) && !((rep & LF_TIES) && (rep & LF_VIOL));
+        const bool ranked = A.rankers && !(rep & LF_FALLBACK) && !((rep & RF_TIES) && (rep & RF_VIOL));
         if (tid == 0 && (rep & (LF_RANKED | LF_FALLBACK)))
-            atomicAdd(&A.dbg[48 + (ranked ? ((rep & LF_TIES) ? 1 : 0) : ((rep & LF_FALLBACK) ? 3 : 2))], 1u);
+            atomicAdd(&A.dbg[48 + (ranked ? ((rep & RF_TIES) ? 1 : 0) : ((rep & LF_FALLBACK) ? 3 : 2))], 1u);
         if (ranked) return;
         lfin_list(Lf);  // the orderer's input (its LDS view then goes over the lfin view)
     }
@@ -656,7 +657,7 @@ tv16_fill(Tv16FillArgs A) {
         uint64_t h0 = ld_sc1(&D.w[0]);
         if (A.lfin) {  // the decision comes from worker 0 of this launch (ticket 0: running)
             uint64_t st1 = 0;
-            for (uint32_t spins = 0; (uint32_t)(h0 >> 32) != ((A.epoch << 8) | TV16_TAG_DEC); ++spins) {
+            for (uint32_t spins = 0; dec_hi(h0) != decision_tag(A.epoch); ++spins) {
                 __builtin_amdgcn_s_sleep(4);
                 h0 = ld_sc1(&D.w[0]);
                 if (spin_expired(spins, st1)) {
@@ -666,10 +667,10 @@ tv16_fill(Tv16FillArgs A) {
             }
         }
         const uint64_t h1 = ld_sc1(&D.w[1]);
-        if ((uint32_t)(h0 >> 32) != ((A.epoch << 8) | TV16_TAG_DEC) || !((uint32_t)h0 & TV16_DEC_B) ||
-            ld_sc1(A.fail) || share > A.helpers || (A.crew && crew_wants((uint32_t)h0, (uint32_t)h1, A.mode, (uint32_t)ld_sc1(&D.w[2]))))
+        if (dec_hi(h0) != decision_tag(A.epoch) || !(dec_lo(h0) & TV16_DEC_B) ||
+            ld_sc1(A.fail) || share > A.helpers || (A.crew && crew_wants(dec_lo(h0), dec_lo(h1), A.mode, dec_lo(ld_sc1(&D.w[2])))))
             return;  // no regime-B fill (or the scan failed, or the crew orders it): nothing to emit
-        if (!(uint32_t)h1 && !((uint32_t)h0 & TV16_DEC_TAIL)) return;  // nothing missing (the orderer returns too)
+        if (!dec_lo(h1) && !(dec_lo(h0) & TV16_DEC_TAIL)) return;  // nothing missing (the orderer returns too)
         uint64_t st0 = 0;
         for (uint32_t spins = 0; ld_sc1(&A.cc->pad[1]) != ready_tag; ++spins) {
             __builtin_amdgcn_s_sleep(4);
@@ -680,7 +681,7 @@ tv16_fill(Tv16FillArgs A) {
         }
         const uint32_t P = ld_sc1(&A.cc->pad[2]), tail_rank = ld_sc1(&A.cc->pad[3]);
         const uint32_t nsh = A.helpers + 1u, chunk = (P + nsh - 1) / nsh;
-        const uint32_t cnt = (uint32_t)(h1 >> 32), rem = d.dst_len - cnt;
+        const uint32_t cnt = dec_hi(h1), rem = d.dst_len - cnt;
         // the share [i0, i1) of the order, as emit_order writes it (scalars
         // taken out of the argument block first: emitting through a reference
         // to it here made the compiler copy the whole block to scratch)
@@ -692,9 +693,9 @@ tv16_fill(Tv16FillArgs A) {
                            reinterpret_cast<uintptr_t>(oval)) & 15u) == 0 && (cnt & 3u) == 0;
         const uint32_t i1 = min(P, (share + 1) * chunk), q = tid & 3u;
         for (uint32_t i = share * chunk + (tid >> 2); i < i1; i += FILL_WG / 4) {
-            const uint32_t o16 = 16u * i - (tail_rank < i ? 16u - tl : 0u);
+            const uint32_t o16 = pop_offset(i, tail_rank, tl);
             if (o16 >= rem) continue;
-            const uint32_t len = min(i == tail_rank ? tl : 16u, rem - o16);
+            const uint32_t len = pop_len(i, tail_rank, tl, o16, rem);
             const uint32_t pos = ld_sc1(&order_g[i]), o = cnt + o16 + 4 * q, bi = pos + 4 * q + ioff;
             if (vec && len == 16 && (o16 & 3u) == 0) {
                 wire_put4(oidx, oval, STG_WIRE_EMIT ? wflag : 0u, wend, o, bi,
@@ -728,28 +729,28 @@ tv16_fill(Tv16FillArgs A) {
     static_assert(PRE * FILL_WG <= CAND_CAP, "prefetch inside the window buffer");
     const uint64_t w0 = ld_sc1(&D.w[0]), w1 = ld_sc1(&D.w[1]), w2 = ld_sc1(&D.w[2]), w3 = ld_sc1(&D.w[3]);
     const uint32_t failed = ld_sc1(A.fail);
-    if ((uint32_t)(w0 >> 32) != ((A.epoch << 8) | TV16_TAG_DEC)) {  // the scan never decided this bucket
+    if (dec_hi(w0) != decision_tag(A.epoch)) {  // the scan never decided this bucket
         if (tid == 0) { g_or(A.fail, FAIL_SPIN_TIMEOUT); st_sc1(d.count_out, POISON_COUNT); }
         return;
     }
-    const uint32_t flags = (uint32_t)w0;
+    // (word by word, not decision_unpack: through the view tv16_fill<false> goes from 59 to 55 SGPR spills)
+    const uint32_t flags = dec_lo(w0);
     if (!(flags & TV16_DEC_B) || failed) return;  // regime A, or the launch already failed
-    const uint32_t cnt = (uint32_t)(w1 >> 32), M = (uint32_t)w1;
-    const uint32_t Wtot = (uint32_t)(w2 >> 32);
-    const float tail_key = u2f((uint32_t)w2);
-    const uint32_t Qtot = (uint32_t)(w3 >> 32);
-    const float t = u2f((uint32_t)w3);
+    const uint32_t cnt = dec_hi(w1), M = dec_lo(w1);
+    const uint32_t Wtot = dec_hi(w2);
+    const float tail_key = u2f(dec_lo(w2));
+    const uint32_t Qtot = dec_hi(w3);
+    const float t = u2f(dec_lo(w3));
     const bool tail = (flags & TV16_DEC_TAIL) != 0;
     const uint32_t N = d.nb - Qtot + (tail ? 1u : 0u);  // candidate vector length
     const uint32_t rem = d.dst_len - cnt;
     if (!M && !tail) return;
-    if (A.crew && crew_wants(flags, M, A.mode, (uint32_t)w2)) return;  // a window miss: the crew orders it (tv16wide.h)
+    if (A.crew && crew_wants(flags, M, A.mode, dec_lo(w2))) return;  // a window miss: the crew orders it (tv16wide.h)
     const uint32_t nhelp = LONE ? A.helpers : 0u;
     CallCtl *const ccp = A.cc;
     const uint32_t tb = f2u(t);
-    const uint32_t wlo = tb > TV16_WIN ? tb - TV16_WIN : 0u;
-    const bool tail_in = tail && tail_key >= u2f(wlo);
-    const bool tail_nan = nan_tail(flags, (uint32_t)w2);  // the literal heap's (tv16wide.h nan_tail)
+    const bool tail_in = tail_in_window(tail, tail_key, tb);
+    const bool tail_nan = nan_tail(flags, dec_lo(w2));  // the literal heap's
     bool fast = (flags & TV16_DEC_WIN) && N <= POS_LIM && Wtot + (tail_in ? 1u : 0u) > 0 && A.mode != 2u &&
                 A.mode != 3u && !tail_nan;
     if (!fast && tid == 0) {  // why the literal heap (debug words 60..63)
@@ -778,7 +779,7 @@ tv16_fill(Tv16FillArgs A) {
         tail_rank = S.flag;
         uint32_t npl = 0;
         for (uint32_t i = tid; i < W; i += FILL_WG) {
-            const uint32_t off = 16u * i - (tail_rank < i ? 16u - d.tl : 0u);
+            const uint32_t off = pop_offset(i, tail_rank, d.tl);
             if (off < rem) npl = max(npl, i + 1);
         }
         npl = wave_max(npl);
@@ -871,7 +872,7 @@ tv16_fill(Tv16FillArgs A) {
         if ((tid & 63u) == 0 && tie_l) S.nv = 1;
         __syncthreads();
         const bool ties = S.nv != 0;
-        const uint32_t covered = 16u * W - (Et != NONE ? 16u - d.tl : 0u);
+        const uint32_t covered = 16u * W - (Et != NONE ? 16u - d.tl : 0u);  // (pops_short written out, likewise: 8 -> 5 or 6)
         fast = covered >= rem;
         if (!fast && tid == 0) atomicAdd(&A.dbg[63], 1u);
         if (fast && !ties) {  // distinct sums: the heap pops them in sum order
@@ -922,7 +923,7 @@ tv16_fill(Tv16FillArgs A) {
         {   // ---- ties without the heap (see (3) above) ----
             if (tid == 0) { S.ntl = 0; S.nel = 0; S.flag2 = 0; }
             __syncthreads();
-            const uint32_t lim = N > P0 + 1 ? N - (P0 + 1) : 0u;
+            const uint32_t lim = pops_late(N, P0);
             for (uint32_t r = tid; r < Rn; r += FILL_WG) {
                 const uint32_t g = S.grp[r];
                 if (g <= P0 && (g != r || (r + 1 < Rn && S.grp[r + 1] == g))) {  // tied, and among the pops
@@ -954,7 +955,7 @@ tv16_fill(Tv16FillArgs A) {
                         const uint32_t p = cix[S.ord[r]];
                         for (uint32_t j = 0; j < nel; ++j) {
                             const uint32_t e = S.el[j];
-                            if (e && (p == (e - 1) / 2 || p == (((e - 1) ^ 1u) + 1))) bad = true;
+                            if (e && (p == heap_parent(e) || p == heap_sibling(e))) bad = true;
                         }
                     }
                 }
@@ -1225,7 +1226,7 @@ tv16_fill(Tv16FillArgs A) {
     // the leader (tv16wide.h) over the window list, when the window holds the
     // top min(P0 + 2, N) candidates (the ragged tail joins as an entry)
     if ((flags & TV16_DEC_WIN) && A.mode != 2u && !tail_nan) {
-        const uint32_t P0 = (rem + 15u) / 16u, seln = min(P0 + 1u, N - 1u);
+        const uint32_t seln = pops_bound(pops_p0(rem), N);
         if (Wtot >= seln + 1u || Wtot + (tail ? 1u : 0u) == N) {
             WideLds &Wl = *reinterpret_cast<WideLds *>(fill_lds);
             LeadIn I;

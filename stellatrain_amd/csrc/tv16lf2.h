@@ -6,7 +6,8 @@
 // (thresholdv16.cpp:138-259: emission order, stage 2's partial line, stage 3's
 // ragged tail, AIMD) and the regime-B heap fill (:261-293).  The results are
 // those of tv16lfin.h (the fill launch's finish of the same lists), which
-// stays behind as the fallback.
+// stays behind as the fallback: both take the regime, the window, the rankers'
+// gate, the pops and the heap keys from tv16_finish.h.
 //
 // Arrival.  Each chunk's counts are stored last (sc1, after the lists are
 // drained) and carry the call's tag.  The last F workgroups of the grid take
@@ -55,8 +56,6 @@ constexpr uint32_t LF2_XB = LBCAP + 1;              // a special bin's entries (
 constexpr uint32_t LF2_XC = 3 * LF2_XB;             // the special bins: the tail's, rank Ph's two candidates
 constexpr uint32_t LF2_PER = LMAXC / LF2_WG;        // chunks per thread in the decision
 constexpr uint32_t LF2_NONE = 0xffffffffu;
-constexpr uint32_t LF2_POS_LIM = (1u << 20) - 1;    // rf_key's 20-bit paths
-constexpr uint32_t LF2_TIES = 1u, LF2_VIOL = 2u;
 constexpr uint32_t LF2_DBG_STALE = 31;            // debug word: workers the freshness check sent to the fill launch (tests read it)
 constexpr uint32_t LF2_RC = 280;                    // a ranker's share of kept entries, at most
 static_assert(LF2_KE * LF2_WG == LF2_WK && LF2_PER * LF2_WG == LMAXC, "per-thread counts");
@@ -83,10 +82,10 @@ struct Lf2Args {
     float t, inc;  // the key's state as this workgroup's scan read it (the state is updated only after every chunk)
 };
 
-struct Lf2Dec {
-    uint32_t Qtot, Wtot, kb, r, lim, c0, ct, cnt, M, N;
-    bool ok, regimeB, tail_cand, listw, lists_ok;  // ok: every chunk was listed in time
-    float t, inc, tail_key;
+struct Lf2Dec : Regime {
+    uint32_t Qtot, Wtot;
+    bool ok, lists_ok;  // ok: every chunk was listed in time
+    float t, inc;
 };
 
 struct Lf2Rk {
@@ -130,8 +129,8 @@ __device__ __forceinline__ float4 ld_sc1_f4(const float4 *base, uint32_t bytes, 
 
 // The decision every role takes: the chunks' counts (sc1, one round trip up to
 // 2,048 chunks, repeated until every chunk carries the call's tag), the
-// ragged tail (thread 0), then the regime as tv16.hip finish_chunk decides
-// it.  Afterwards qp16[c] holds min(qualifying lines before chunk c, 65535):
+// ragged tail (thread 0), then the regime (tv16_finish.h).  Afterwards
+// qp16[c] holds min(qualifying lines before chunk c, 65535):
 // exact wherever it is below lim (lim = dst_len / 16 + 1 < 2^16 on this path,
 // LMAXC chunks of LCHUNK lines, k <= n), which is all the roles use.
 constexpr uint32_t kLf2PollSleep = 2;  // s_sleep between the finishers' descriptor polls (64 cycles a unit)
@@ -139,7 +138,9 @@ constexpr uint32_t kLf2PollSleep = 2;  // s_sleep between the finishers' descrip
 // one wave, its wait, then a workgroup barrier before any load of the lists
 // (MI355X guide, "Valid forms", Consumer).  The lists are stored sc1 and
 // loaded sc1, which the guide's table validates in place of the acquire only
-// at one workgroup per CU; the scan runs eight per CU, so the acquire stays.
+// at one workgroup per CU; the plain and error-feedback scans run eight per
+// CU and the gather scans as many as their registers allow (tv16lone.hip
+// tv16_lscan), always more than one, so the acquire stays.
 __device__ __forceinline__ void lf2_acquire() {
     if (threadIdx.x < 64) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -214,35 +215,25 @@ __device__ __forceinline__ void lf2_decide(Lf2Lds &L, Lf2Dec &D, uint32_t (&h)[4
         pq += q;
     }
     D.lists_ok = !__syncthreads_or((int)bad);
-    const uint32_t Qtot = D.Qtot, dst_len = A.dst_len;
-    D.kb = dst_len / 16;
-    D.r = dst_len % 16;
-    D.lim = D.kb + (D.r ? 1u : 0u);
-    D.c0 = Qtot >= D.lim ? dst_len : 16u * Qtot;
-    if (tid == 0) {  // stage 3: the ragged tail's signed, sequential sum (thresholdv16.cpp:212-236)
-        uint32_t ct = 0, cand = 0;
-        float key = 0.f;
-        if (D.c0 < dst_len && A.tl) {
+    const uint32_t dst_len = A.dst_len;
+    regime_head(D, dst_len, D.Qtot);
+    if (tid == 0) {  // stage 3: the ragged tail's signed, sequential sum
+        regime_no_tail(D);
+        if (regime_sums_tail(D, dst_len, A.tl)) {
             float sm = 0.f;
             for (uint32_t i = 0; i < A.tl; ++i) sm += L.tail[i];
-            if (sm * 16.0f >= D.t * (float)A.tl) ct = min(dst_len - D.c0, A.tl);
-            else { cand = 1; key = sm * 16.0f / (float)A.tl; }
+            regime_tail(D, sm, D.t, A.tl, dst_len);
         }
-        L.v[0] = ct;
-        L.v[1] = cand;
-        L.v[2] = f2u(key);
+        L.v[0] = D.ct;
+        L.v[1] = D.tail_cand ? 1u : 0u;
+        L.v[2] = f2u(D.tail_key);
     }
     __syncthreads();
     D.ct = L.v[0];
     D.tail_cand = L.v[1] != 0;
     D.tail_key = u2f(L.v[2]);
     __syncthreads();
-    D.cnt = D.c0 + D.ct;
-    D.regimeB = D.cnt < dst_len;
-    const uint32_t ncand = A.nb - Qtot;  // non-qualifying full lines
-    D.M = D.regimeB ? min((dst_len - D.cnt + 15u) / 16u, ncand) : 0u;
-    D.listw = D.regimeB && D.Wtot >= D.M && D.Wtot + 1 <= CAND_CAP;
-    D.N = ncand + (D.tail_cand ? 1u : 0u);  // the reference's candidate vector length
+    regime_close(D, dst_len, A.nb, D.Qtot, D.Wtot);
 }
 
 // one quarter (four floats) of a qualifying line at its global rank g (lfin_store)
@@ -323,7 +314,7 @@ __device__ __forceinline__ bool lf2_worker(Lf2Lds &L, uint32_t wk) {
         if (tid == 0) g_add(&A.dbg[LF2_DBG_STALE], 1u);
         return false;
     }
-    // worker 0: tail, AIMD state, count (tv16.hip finish_chunk, lfin_worker)
+    // worker 0: tail, AIMD state, count (as lfin_worker)
     if (wk == 0 && tid == 0) {
         const size_t p0 = (size_t)A.nb * 16;
         for (uint32_t i = 0; i < D.ct; ++i) {
@@ -334,10 +325,10 @@ __device__ __forceinline__ bool lf2_worker(Lf2Lds &L, uint32_t wk) {
             for (uint32_t i = 0; i < A.tl; ++i)
                 *gp(A.resid + p0 + i) = u2f(ld_sc1(reinterpret_cast<const uint32_t *>(A.src) + p0 + i));
         auto st = gp(A.state);
-        st->t = D.regimeB ? (float)((double)D.t * 0.99) : D.t + D.inc;  // thresholdv16.cpp:243-259
+        st->t = next_threshold(D.t, D.inc, D.regimeB);
         st->inc = D.inc;
         st->init = 1;
-        st_sc1(A.count_out, (uint32_t)min((uint64_t)A.dst_len, (uint64_t)A.nb * 16 + A.tl));
+        st_sc1(A.count_out, emitted_count(A.dst_len, A.nb, A.tl));
         if (ld_sc1(A.fail)) st_sc1(A.count_out, POISON_COUNT);
     }
     if (wk == 0) LF2_STAMP(4);
@@ -361,16 +352,11 @@ __device__ __forceinline__ bool lf2_ranker(Lf2Lds &L, uint32_t rk) {
         return false;
     };
     if (!D.regimeB || (!D.M && !D.tail_cand)) return true;  // nothing to fill
-    const uint32_t tb = f2u(D.t), wlo = tb > TV16_WIN ? tb - TV16_WIN : 0u;
-    const bool tail_in = D.tail_cand && D.tail_key >= u2f(wlo);
-    const uint32_t W = D.Wtot + (tail_in ? 1u : 0u);
-    // (the conditions of lfin_ranker; a -0.0 tail ties +0.0 sums in the
-    // reference's float compare, not in this key order; prefixes fit u16)
-    if (!D.listw || !D.lists_ok || D.N > LF2_POS_LIM || W == 0 || A.mode || D.Qtot > 0xffffu ||
-        (tail_in && (f2u(D.tail_key) & 0x80000000u)) || (tail_in && !(D.tail_key < D.t)) ||
-        (D.tail_cand && D.tail_key != D.tail_key))  // (a NaN tail: tv16wide.h nan_tail)
+    if (!rankers_can_take(D, D.Wtot, D.lists_ok, A.mode, D.t, POS_LIM) || D.Qtot > 0xffffu)  // (prefixes fit u16)
         return fail_at(1);
-    const uint32_t tw = tail_in ? tb - 1u - f2u(D.tail_key) : 0u, tbin = tail_in ? tw >> 8 : LF2_NONE;
+    const uint32_t tb = f2u(D.t);
+    const bool tail_in = tail_in_window(D.tail_cand, D.tail_key, tb);
+    const uint32_t tw = tail_in ? window_offset(tb, f2u(D.tail_key)) : 0u, tbin = tail_in ? window_bin(tw) : LF2_NONE;
     const uint32_t need = D.M + 2, rem = A.dst_len - D.cnt;
     // ---- bin starts; the first bins holding need entries are kept ----
     {
@@ -403,14 +389,14 @@ __device__ __forceinline__ bool lf2_ranker(Lf2Lds &L, uint32_t rk) {
     bool over = false;
 #pragma unroll
     for (uint32_t u = 0; u < 4; ++u) over |= (4 * tid + u < cut && h[u] > LBCAP);
-    if (__syncthreads_or((int)over) || Wk > LF2_WK || Wk == 0 || 16u * Wk < rem) return fail_at(2);
+    if (__syncthreads_or((int)over) || Wk > LF2_WK || Wk == 0 || pops_short(Wk, false, A.tl, rem)) return fail_at(2);
     // ---- one parallel pass (every thread its four bins and its chunks, no
     //      dependent searches): this ranker's bins [b_lo, b_hi) (the first bins
     //      starting at or past ceil(rk Wk / NR) and ceil((rk + 1) Wk / NR)), the
     //      bins holding ranks ra and rb (rank Ph's candidates), and the first
     //      chunk that may hold a candidate position >= late_min ----
-    const uint32_t P0 = (rem + 15u) / 16u;
-    const uint32_t ra = min(P0 + 1u, Wk - 1u), rb = min(P0 + 2u, Wk - 1u);
+    const uint32_t P0 = pops_p0(rem);
+    const uint32_t ra = pops_bound(P0, Wk), rb = pops_bound(P0 + 1u, Wk);
     const uint32_t x_lo = (uint32_t)(((uint64_t)rk * Wk + NR - 1) / NR), x_hi = (uint32_t)(((uint64_t)(rk + 1) * Wk + NR - 1) / NR);
     const uint32_t late_min = D.N > Wk + 1 ? D.N - (Wk + 1) : 0u;
     if (tid == 0) { L.v[5] = x_lo ? cut : 0u; L.v[6] = x_hi ? cut : 0u; }
@@ -484,10 +470,10 @@ __device__ __forceinline__ bool lf2_ranker(Lf2Lds &L, uint32_t rk) {
         if (A.skip == 2) { vm_drain(); return false; }
         if (STG_LF2_STAMPS && rk == 0) { vm_drain(); LF2_STAMP(11); }
         auto decode = [&](uint64_t v, uint32_t &w, uint32_t &cx, uint32_t &line) {  // a binned window entry
-            const uint32_t sx = (uint32_t)v, yy = (uint32_t)(v >> 32), c = yy >> 19;
-            line = c * LCHUNK + ((yy >> 10) & 511u);
-            w = tb - 1u - sx;
-            cx = line - ((uint32_t)L.qp16[c] + (yy & 1023u));
+            const WinEntry we = win_entry((uint32_t)v, (uint32_t)(v >> 32), tb, LCHUNK);
+            line = we.line;
+            w = we.w;
+            cx = win_cand(we, L.qp16[we.c]);
         };
 #pragma unroll
         for (uint32_t j = 0; j < 2; ++j) {
@@ -501,7 +487,7 @@ __device__ __forceinline__ bool lf2_ranker(Lf2Lds &L, uint32_t rk) {
             } else {
                 decode(y[j], w, cx, line);
             }
-            L.u.r.kg[i] = (uint64_t)w << 25 | rf_key(cx);
+            L.u.r.kg[i] = rank_key(w, cx);
             L.u.r.kc[i] = cx;
             L.u.r.kl[i] = line;
             L.u.r.kb[i] = (uint16_t)bj[j];
@@ -510,13 +496,13 @@ __device__ __forceinline__ bool lf2_ranker(Lf2Lds &L, uint32_t rk) {
             uint32_t w, cx, line;
             if (is_tail(L.bin[sbk] + xi, sbk)) { w = tw; cx = D.N - 1; }
             else decode(yx, w, cx, line);
-            L.u.r.xg[k * LF2_XB + xi] = (uint64_t)w << 25 | rf_key(cx);
+            L.u.r.xg[k * LF2_XB + xi] = rank_key(w, cx);
         }
         // late candidates: window lines of the last chunks starting at >= late_min, and the tail
         if (lc_c < A.nc && lc_s < (((uint32_t)dl >> 16) & 0xffffu) && lc_s < LWCAP) {
             const uint32_t sx = (uint32_t)yl, yy = (uint32_t)(yl >> 32);
             const uint32_t line = lc_c * LCHUNK + (yy & 0xffffu);
-            const uint32_t cx = line - ((uint32_t)L.qp16[lc_c] + (yy >> 16)), w = tb - 1u - sx;
+            const uint32_t cx = line - ((uint32_t)L.qp16[lc_c] + (yy >> 16)), w = window_offset(tb, sx);
             if (cx >= late_min && cx) {
                 const uint32_t i = atomicAdd(&L.v[7], 1u);
                 if (i < 64) { L.u.r.lc[i] = cx; L.u.r.lw[i] = w; }
@@ -557,16 +543,13 @@ __device__ __forceinline__ bool lf2_ranker(Lf2Lds &L, uint32_t rk) {
             const uint32_t r = inbin_rank(0, n, g);
             tr = L.bin[sb0] + (uint32_t)__builtin_amdgcn_readlane((int)r, (int)(n - 1));
         }
-        uint32_t P = P0;
-        if (tr < P) P = (rem + (16u - A.tl) + 15u) / 16u;
-        P = min(P, Wk);
-        const uint32_t Ph = min(P + 1, Wk - 1);
+        const uint32_t P = umin(pops_count(rem, A.tl, tr), Wk), Ph = pops_bound(P, Wk);
         const uint32_t k = Ph == ra ? 1u : 2u, b = k == 1 ? sb1 : sb2, n = L.bin[b + 1] - L.bin[b];
         const uint32_t want = Ph - L.bin[b];
         // the bin's entries are distinct keys: exactly one has `want` smaller
         uint64_t g;
         const uint32_t r = inbin_rank(k, n, g);
-        uint32_t hit = (lane < n && r == want) ? (uint32_t)(g >> 25) + 1u : 0u;
+        uint32_t hit = (lane < n && r == want) ? rank_key_offset(g) + 1u : 0u;
         hit = wave_max(hit);
         if (lane == 0) {
             L.v[9] = tr;
@@ -579,20 +562,20 @@ __device__ __forceinline__ bool lf2_ranker(Lf2Lds &L, uint32_t rk) {
     for (uint32_t i = tid; i < ne; i += LF2_WG) {
         const uint32_t b = L.u.r.kb[i], lo = L.bin[b] - E0, hi = L.bin[b + 1] - E0;
         const uint64_t ge = L.u.r.kg[i];
-        const uint32_t we = (uint32_t)(ge >> 25);
+        const uint32_t we = rank_key_offset(ge);
         uint32_t r = lo;
         bool tie = false;
         for (uint32_t x = lo; x < hi; ++x) {
             const uint64_t gx = L.u.r.kg[x];
             r += gx < ge;
-            tie |= (uint32_t)(gx >> 25) == we && gx != ge;
+            tie |= rank_key_offset(gx) == we && gx != ge;
         }
         uint32_t f = 0;
         if (tie) {  // rare: is a tied line's start below this one's?
-            f = LF2_TIES;
+            f = RF_TIES;
             const uint32_t qe = L.u.r.kc[i] + 1;
             for (uint32_t x = lo; x < hi; ++x)
-                if (x != i && (uint32_t)(L.u.r.kg[x] >> 25) == we && is_desc(L.u.r.kc[x] + 1, qe)) f |= LF2_VIOL;
+                if (x != i && rank_key_offset(L.u.r.kg[x]) == we && is_desc(L.u.r.kc[x] + 1, qe)) f |= RF_VIOL;
         }
         L.u.r.tf[i] = (uint8_t)f;
         L.u.r.ord[r] = (uint16_t)i;
@@ -600,8 +583,8 @@ __device__ __forceinline__ bool lf2_ranker(Lf2Lds &L, uint32_t rk) {
     __syncthreads();
     if (rk == 0) LF2_STAMP(14);
     const uint32_t tr = L.v[9], P = L.v[10], Ph = L.v[11], wh = L.v[12];
-    if (!L.v[13] || (tr != LF2_NONE && 16u * Wk - (16u - A.tl) < rem)) return fail_at(4);
-    const uint32_t late = D.N > Ph + 1 ? D.N - (Ph + 1) : 0u;  // start positions >= late: the last Ph + 1
+    if (!L.v[13] || pops_short(Wk, tr != LF2_NONE, A.tl, rem)) return fail_at(4);
+    const uint32_t late = pops_late(D.N, Ph);
     if (L.v[7] > 64) return fail_at(5);  // (every ranker sees the same count)
     // ---- the share's pops (ranks [E0, min(E1, P)), four lanes per line):
     //      their loads go out now, the stores wait for the checks ----
@@ -618,9 +601,9 @@ __device__ __forceinline__ bool lf2_ranker(Lf2Lds &L, uint32_t rk) {
             len[u] = 0;
             v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (i < s1) {
-                off[u] = 16u * i - (tr < i ? 16u - A.tl : 0u);
+                off[u] = pop_offset(i, tr, A.tl);
                 if (off[u] < rem) {
-                    len[u] = min(i == tr ? A.tl : 16u, rem - off[u]);
+                    len[u] = pop_len(i, tr, A.tl, off[u], rem);
                     pos[u] = L.u.r.kl[L.u.r.ord[i - E0]] * 16u;
                     if (vec && len[u] == 16 && (off[u] & 3u) == 0) v[u] = ld_sc1_f4(reinterpret_cast<const float4 *>(A.src), src_bytes, pos[u] / 4 + q);
                 }
@@ -655,18 +638,17 @@ __device__ __forceinline__ bool lf2_ranker(Lf2Lds &L, uint32_t rk) {
     // ---- the fast path's conditions (tv16fill.hip (3)) for the share's R ----
     uint32_t fl = 0;
     const uint32_t nl = L.v[8];
-    if (nl > 64) fl |= LF2_VIOL;
+    if (nl > 64) fl |= RF_VIOL;
     for (uint32_t i = tid; i < ne; i += LF2_WG) {
-        if ((uint32_t)(L.u.r.kg[i] >> 25) > wh) continue;
+        if (rank_key_offset(L.u.r.kg[i]) > wh) continue;
         fl |= L.u.r.tf[i];
         const uint32_t cf = L.u.r.kc[i];
         for (uint32_t x = 0; x < min(nl, 64u); ++x) {
-            const uint32_t ce = L.u.r.late[x];
-            if (cf == (ce - 1) / 2 || cf == ((ce - 1) ^ 1u) + 1) fl |= LF2_VIOL;
+            if (parent_or_sibling(cf, L.u.r.late[x])) fl |= RF_VIOL;
         }
     }
-    const bool viol = __syncthreads_or((int)(fl & LF2_VIOL));
-    const bool ties = __syncthreads_or((int)(fl & LF2_TIES));
+    const bool viol = __syncthreads_or((int)(fl & RF_VIOL));
+    const bool ties = __syncthreads_or((int)(fl & RF_TIES));
     if (viol) return fail_at(6);
     if (rk == 0) LF2_STAMP(6);
     store_round();

@@ -4,15 +4,17 @@
 //
 // Reference: ThresholdvCompressor16::impl_simd_v2 after the streaming
 // (thresholdv16.cpp:138-259: emission order, stage 2's partial line, stage 3's
-// ragged tail, AIMD) and the regime-B heap fill (:261-293).
+// ragged tail, AIMD) and the regime-B heap fill (:261-293).  The rules this
+// finish shares with tv16.hip finish_chunk and tv16lf2.h (the regime, the
+// Decision words, the window, the pops' offsets, the heap keys) are the
+// functions of tv16_finish.h.
 //
 // The scan left per chunk of LCHUNK lines its counts (ldesc), its qualifying
 // lines in order with their data (lq, lv) and its window lines in order (lw:
 // {sum bits, line within the chunk | qualifying lines before it << 16}).
 // Three roles share the launch, none waits on another:
 //   workers  (tickets [0, workers))  take the chunks' prefix counts, decide
-//            the regime exactly as the batched scan's last chunk does
-//            (tv16.hip finish_chunk), write a balanced share of the
+//            the regime (tv16_finish.h Regime), write a balanced share of the
 //            qualifying lines at their global ranks and of the window list in
 //            scan order (the exact orderer's input); worker 0 writes the
 //            ragged tail, the AIMD state, the count and the decision;
@@ -60,7 +62,7 @@ struct LfinLds {
             uint32_t kl[EMAX];         // ... line (the ragged tail: nb)
             uint16_t emap[EMAX];       // ... its bin
             uint16_t ord[EMAX];        // rank -> kept entry
-            uint8_t tf[EMAX];          // ... LF_TIES / LF_VIOL if it turns out to be in R
+            uint8_t tf[EMAX];          // ... RF_TIES / RF_VIOL if it turns out to be in R
         } r;
         struct {                       // worker: rank -> chunk
             uint16_t qmap[LF_QMAP];
@@ -82,9 +84,7 @@ __device__ __forceinline__ uint32_t chunk_of(const uint32_t *p, uint32_t nc, uin
     return lo;
 }
 
-// ranker report bits (CallCtl pad[5])
-constexpr uint32_t LF_TIES = 1u;      // equal sums among the first pops + 1
-constexpr uint32_t LF_VIOL = 2u;      // a fast-path condition failed for a tied or late line
+// ranker report bits (CallCtl pad[5]): RF_TIES, RF_VIOL (tv16_finish.h) and
 constexpr uint32_t LF_FALLBACK = 4u;  // the rankers could not order this call at all
 constexpr uint32_t LF_RANKED = 8u;    // a regime-B call the rankers took
 
@@ -108,14 +108,13 @@ constexpr uint32_t LF_RANKED = 8u;    // a regime-B call the rankers took
     } while (0)
 
 // What every lfin workgroup decides, identically.
-struct LfinDec {
-    uint32_t Qtot, Wtot, kb, r, lim, c0, ct, cnt, M, N;
-    bool regimeB, tail_cand, listw, lists_ok, any_big;  // any_big: a chunk lists more than LF_SPEC lines
-    float t, inc, tail_key;
+struct LfinDec : Regime {
+    uint32_t Qtot, Wtot;
+    bool lists_ok, any_big;  // any_big: a chunk lists more than LF_SPEC lines
+    float t, inc;
 };
 
-// Per-chunk counts -> exclusive prefixes in LDS, and the regime decision of
-// tv16.hip finish_chunk (thresholdv16.cpp:138-259).
+// Per-chunk counts -> exclusive prefixes in LDS, and the regime decision.
 __device__ __forceinline__ void lfin_prefix(LfinLds &L, const LfinArgs &A, LfinDec &D) {
     const Tv16FillBucket &d = A.d;
     const uint32_t tid = threadIdx.x, nc = A.nc;
@@ -154,28 +153,16 @@ __device__ __forceinline__ void lfin_prefix(LfinLds &L, const LfinArgs &A, LfinD
     if (tid == 0) { L.qp[nc] = D.Qtot; L.wp[nc] = D.Wtot; }
     D.lists_ok = !__syncthreads_or((int)bad);
     D.any_big = __syncthreads_or((int)big);
-    const uint32_t Qtot = D.Qtot;
-    D.kb = d.dst_len / 16;
-    D.r = d.dst_len % 16;
-    D.lim = D.kb + (D.r ? 1u : 0u);
-    D.c0 = Qtot >= D.lim ? d.dst_len : 16u * Qtot;
-    D.tail_cand = false;
-    D.tail_key = 0.f;
-    D.ct = 0;
-    if (D.c0 < d.dst_len && d.tl) {  // stage 3: the ragged tail's signed, sequential sum (thresholdv16.cpp:212-236)
+    regime_head(D, d.dst_len, D.Qtot);
+    regime_no_tail(D);
+    if (regime_sums_tail(D, d.dst_len, d.tl)) {  // stage 3: the ragged tail's signed, sequential sum
         float sm = 0.f;
 #pragma unroll
         for (uint32_t i = 0; i < 16; ++i)
             if (i < d.tl) sm += tv[i];
-        if (sm * 16.0f >= D.t * (float)d.tl) D.ct = min(d.dst_len - D.c0, d.tl);
-        else { D.tail_cand = true; D.tail_key = sm * 16.0f / (float)d.tl; }
+        regime_tail(D, sm, D.t, d.tl, d.dst_len);
     }
-    D.cnt = D.c0 + D.ct;
-    D.regimeB = D.cnt < d.dst_len;
-    const uint32_t ncand = d.nb - Qtot;  // non-qualifying full lines
-    D.M = D.regimeB ? min((d.dst_len - D.cnt + 15u) / 16u, ncand) : 0u;
-    D.listw = D.regimeB && D.Wtot >= D.M && D.Wtot + 1 <= CAND_CAP;
-    D.N = ncand + (D.tail_cand ? 1u : 0u);  // the reference's candidate vector length
+    regime_close(D, d.dst_len, d.nb, D.Qtot, D.Wtot);
 }
 
 // A chunk whose lists overflowed, read again from src by one workgroup, in
@@ -185,7 +172,7 @@ __device__ __forceinline__ void lfin_rescan(LfinLds &L, const Tv16FillBucket &d,
     const uint32_t tid = threadIdx.x;
     const uint32_t L0 = c * LCHUNK;
     const uint32_t nl = d.nb > L0 ? min(LCHUNK, d.nb - L0) : 0u;
-    const uint32_t tb = f2u(D.t), wlo = tb > TV16_WIN ? tb - TV16_WIN : 0u;
+    const uint32_t tb = f2u(D.t), wlo = window_lo(tb);
     const bool vec = aligned16(d);
     uint32_t *cu = const_cast<uint32_t *>(d.cand), *cl = cu + CAND_CAP, *ci = cu + 2 * CAND_CAP;
     uint32_t qb = L.qp[c], wb = L.wp[c];
@@ -298,19 +285,18 @@ __device__ __noinline__ void lfin_worker(LfinLds &L, uint32_t wk) {
         }
         if (A.resid && d.tl)  // fused error feedback: the ragged tail is not streamed
             for (uint32_t i = 0; i < d.tl; ++i) A.resid[(size_t)d.nb * 16 + i] = d.src[(size_t)d.nb * 16 + i];
-        A.state->t = D.regimeB ? (float)((double)D.t * 0.99) : D.t + D.inc;  // thresholdv16.cpp:243-259
+        A.state->t = next_threshold(D.t, D.inc, D.regimeB);
         A.state->inc = D.inc;
         A.state->init = 1;
-        st_sc1(d.count_out, (uint32_t)min((uint64_t)d.dst_len, (uint64_t)d.nb * 16 + d.tl));
+        st_sc1(d.count_out, emitted_count(d.dst_len, d.nb, d.tl));
         if (ld_sc1(A.fail)) st_sc1(d.count_out, POISON_COUNT);
-        uint32_t flags = 0;
-        if (D.regimeB) flags = TV16_DEC_B | (D.tail_cand ? TV16_DEC_TAIL : 0u) | (D.listw ? TV16_DEC_WIN : 0u);
+        const DecisionWords dw = decision_pack(D, D.Wtot, D.Qtot, D.t, decision_tag(A.epoch));
         Decision &Dc = A.dec[0];
-        st_sc1(&Dc.w[1], ((uint64_t)D.cnt << 32) | D.M);
-        st_sc1(&Dc.w[2], ((uint64_t)D.Wtot << 32) | __float_as_uint(D.tail_key));
-        st_sc1(&Dc.w[3], ((uint64_t)D.Qtot << 32) | __float_as_uint(D.t));
+        st_sc1(&Dc.w[1], dw.w[1]);
+        st_sc1(&Dc.w[2], dw.w[2]);
+        st_sc1(&Dc.w[3], dw.w[3]);
         vm_drain();
-        st_sc1(&Dc.w[0], ((uint64_t)((A.epoch << 8) | TV16_TAG_DEC) << 32) | flags);
+        st_sc1(&Dc.w[0], dw.w[0]);
     }
     LF_WSTAMP(5);
 }
@@ -369,12 +355,15 @@ __device__ __noinline__ void lfin_ranker(LfinLds &L, uint32_t rk) {
         if (rk == 0 && threadIdx.x == 0) g_or(&A.cc->pad[5], LF_FALLBACK);
     };
     if (rk == 0 && tid == 0) g_or(&A.cc->pad[5], LF_RANKED);
-    const uint32_t tb = f2u(D.t), wlo = tb > TV16_WIN ? tb - TV16_WIN : 0u;
-    const bool tail_in = D.tail_cand && D.tail_key >= u2f(wlo);
+    const uint32_t tb = f2u(D.t);
+    const bool tail_in = tail_in_window(D.tail_cand, D.tail_key, tb);
     const uint32_t W = D.Wtot + (tail_in ? 1u : 0u);
+    // The conditions of rankers_can_take (tv16_finish.h) written out: through the
+    // helper, in every form and position tried, the wire build's tv16_fill<true>
+    // goes from 215 to 217 or more SGPR spills.
     // a -0.0 tail ties +0.0 sums in the reference's float compare, not in ford() order
     if (!D.listw || !D.lists_ok || D.N > POS_LIM || W == 0 || A.mode ||
-        (tail_in && (f2u(D.tail_key) & 0x80000000u)) || (D.tail_cand && D.tail_key != D.tail_key)) {  // (a NaN tail: tv16wide.h nan_tail)
+        (tail_in && (f2u(D.tail_key) & 0x80000000u)) || (D.tail_cand && D.tail_key != D.tail_key)) {  // (a NaN tail: tv16_finish.h nan_tail)
         give_up();
         return;
     }
@@ -384,7 +373,7 @@ __device__ __noinline__ void lfin_ranker(LfinLds &L, uint32_t rk) {
         give_up();
         return;
     }
-    const uint32_t tw = tail_in ? tb - 1u - f2u(D.tail_key) : 0u, tbin = tail_in ? tw >> 8 : NONE;
+    const uint32_t tw = tail_in ? window_offset(tb, f2u(D.tail_key)) : 0u, tbin = tail_in ? window_bin(tw) : NONE;
     // ---- bin starts; keep the first bins holding M + 2 entries: every pop,
     //      the first line past them and its ties (a bin never splits equal sums) ----
     const uint32_t need = D.M + 2;
@@ -408,7 +397,7 @@ __device__ __noinline__ void lfin_ranker(LfinLds &L, uint32_t rk) {
     const uint32_t rem = d.dst_len - D.cnt;
     // a kept bin with more entries than the scan could store, or too many kept
     const bool over = (PB * tid < cut && h[0] > LBCAP) || (PB * tid + 1 < cut && h[1] > LBCAP);
-    if (__syncthreads_or((int)over) || Wk > EMAX || Wk == 0 || 16u * Wk < rem) {
+    if (__syncthreads_or((int)over) || Wk > EMAX || Wk == 0 || pops_short(Wk, false, d.tl, rem)) {
         give_up();
         return;
     }
@@ -448,12 +437,12 @@ __device__ __noinline__ void lfin_ranker(LfinLds &L, uint32_t rk) {
                 cx = D.N - 1;
                 line = d.nb;
             } else {
-                const uint32_t c = x[j].y >> 19;
-                line = c * LCHUNK + ((x[j].y >> 10) & 511u);
-                w = tb - 1u - x[j].x;
-                cx = line - (L.qp[c] + (x[j].y & 1023u));
+                const WinEntry we = win_entry(x[j].x, x[j].y, tb, LCHUNK);
+                line = we.line;
+                w = we.w;
+                cx = win_cand(we, L.qp[we.c]);
             }
-            kg[e] = (uint64_t)w << 25 | rf_key(cx);
+            kg[e] = rank_key(w, cx);
             kc[e] = cx;
             kl[e] = line;
         }
@@ -467,20 +456,20 @@ __device__ __noinline__ void lfin_ranker(LfinLds &L, uint32_t rk) {
     for (uint32_t e = tid; e < Wk; e += FILL_WG) {
         const uint32_t b = emap[e], lo = L.bin[b], hi = L.bin[b + 1];
         const uint64_t ge = kg[e];
-        const uint32_t we = (uint32_t)(ge >> 25);
+        const uint32_t we = rank_key_offset(ge);
         uint32_t r = lo;
         bool tie = false;
         for (uint32_t x = lo; x < hi; ++x) {
             const uint64_t gx = kg[x];
             r += gx < ge;
-            tie |= (uint32_t)(gx >> 25) == we && gx != ge;
+            tie |= rank_key_offset(gx) == we && gx != ge;
         }
         uint32_t f = 0;
         if (tie) {  // rare: is a tied line's start below this one's?
-            f = LF_TIES;
+            f = RF_TIES;
             const uint32_t qe = kc[e] + 1;
             for (uint32_t x = lo; x < hi; ++x)
-                if (x != e && (uint32_t)(kg[x] >> 25) == we && is_desc(kc[x] + 1, qe)) f |= LF_VIOL;
+                if (x != e && rank_key_offset(kg[x]) == we && is_desc(kc[x] + 1, qe)) f |= RF_VIOL;
         }
         tf[e] = (uint8_t)f;
         ord[r] = (uint16_t)e;
@@ -490,23 +479,17 @@ __device__ __noinline__ void lfin_ranker(LfinLds &L, uint32_t rk) {
     LF_STAMP(4);
     // ---- the pops P and the bound Ph of tv16fill.hip; R = keys >= the key at rank Ph ----
     const uint32_t tr = L.tail_rank;
-    if (tr != NONE && 16u * Wk - (16u - d.tl) < rem) {
+    if (tr != NONE && pops_short(Wk, true, d.tl, rem)) {
         give_up();
         return;
     }
-    uint32_t P = (rem + 15u) / 16u;  // the first rank whose output offset reaches rem
-    if (tr < P) P = (rem + (16u - d.tl) + 15u) / 16u;
-    P = min(P, Wk);
-    // conservative bounds for the fast-path conditions: one more pop than P
-    // (the exact orderer counts its pops in (sum desc, index asc) order)
-    const uint32_t Ph = min(P + 1, Wk - 1);
-    const uint32_t late = D.N > Ph + 1 ? D.N - (Ph + 1) : 0u;  // start positions >= late: the last Ph + 1
+    const uint32_t P = umin(pops_count(rem, d.tl, tr), Wk), Ph = pops_bound(P, Wk);
+    const uint32_t late = pops_late(D.N, Ph);  // start positions >= late: the last Ph + 1
     // ---- this ranker's share of the pops: four lanes per line, the loads of
     //      NRD rounds in flight (issued now, stored after the checks) ----
     const uint32_t nr = A.rankers, per = (P + nr - 1) / nr;
     const uint32_t s0 = min(P, rk * per), s1 = min(P, s0 + per);
     const bool vec = aligned16(d) && (D.cnt & 3u) == 0;
-    auto offset = [&](uint32_t i) { return 16u * i - (tr < i ? 16u - d.tl : 0u); };
     constexpr uint32_t LPR = FILL_WG / 4, NRD = 4;
     const uint32_t q = tid & 3u;
     float4 v0, v1, v2, v3;
@@ -517,9 +500,9 @@ __device__ __noinline__ void lfin_ranker(LfinLds &L, uint32_t rk) {
             const uint32_t i = (J0) + u * LPR + (tid >> 2);                                 \
             len[u] = 0;                                                                     \
             if (i < s1) {                                                                   \
-                off[u] = offset(i);                                                         \
+                off[u] = pop_offset(i, tr, d.tl);                                           \
                 if (off[u] < rem) {                                                         \
-                    len[u] = min(i == tr ? d.tl : 16u, rem - off[u]);                       \
+                    len[u] = pop_len(i, tr, d.tl, off[u], rem);                             \
                     pos[u] = kl[ord[i]] * 16;                                               \
                 }                                                                           \
             }                                                                               \
@@ -546,10 +529,10 @@ __device__ __noinline__ void lfin_ranker(LfinLds &L, uint32_t rk) {
     LF_LOAD_ROUND(s0);
     // ---- the fast path's conditions (tv16fill.hip (3)) for R; every ranker
     //      finds the same, ranker 0 reports ----
-    const uint32_t wh = (uint32_t)(kg[ord[Ph]] >> 25);  // R: window offsets <= wh
+    const uint32_t wh = rank_key_offset(kg[ord[Ph]]);  // R: window offsets <= wh
     uint32_t fl = 0;
     for (uint32_t e = tid; e < Wk; e += FILL_WG) {
-        if ((uint32_t)(kg[e] >> 25) > wh) continue;
+        if (rank_key_offset(kg[e]) > wh) continue;
         fl |= tf[e];
         const uint32_t ce = kc[e];
         if (ce >= late && ce) {  // a late line of R
@@ -560,14 +543,14 @@ __device__ __noinline__ void lfin_ranker(LfinLds &L, uint32_t rk) {
     __syncthreads();
     {   // no line of R at a late line's parent or sibling
         const uint32_t nl = L.nlate;
-        if (nl > 64) fl |= LF_VIOL;
+        if (nl > 64) fl |= RF_VIOL;
         else if (nl)
             for (uint32_t f = tid; f < Wk; f += FILL_WG) {
-                if ((uint32_t)(kg[f] >> 25) > wh) continue;
+                if (rank_key_offset(kg[f]) > wh) continue;
                 const uint32_t cf = kc[f];
                 for (uint32_t i = 0; i < nl; ++i) {
                     const uint32_t ce = L.late[i];
-                    if (cf == (ce - 1) / 2 || cf == ((ce - 1) ^ 1u) + 1) fl |= LF_VIOL;
+                    if (cf == heap_parent(ce) || cf == heap_sibling(ce)) fl |= RF_VIOL;
                 }
             }
     }
@@ -578,9 +561,9 @@ __device__ __noinline__ void lfin_ranker(LfinLds &L, uint32_t rk) {
         store1(0, v0); store1(1, v1); store1(2, v2); store1(3, v3);
     }
 #undef LF_LOAD_ROUND
-    const bool ties = __syncthreads_or((int)(fl & LF_TIES));
-    const bool viol = __syncthreads_or((int)(fl & LF_VIOL));
-    if (rk == 0 && tid == 0 && (viol || ties)) g_or(&A.cc->pad[5], (ties ? LF_TIES : 0u) | (viol ? LF_VIOL : 0u));
+    const bool ties = __syncthreads_or((int)(fl & RF_TIES));
+    const bool viol = __syncthreads_or((int)(fl & RF_VIOL));
+    if (rk == 0 && tid == 0 && (viol || ties)) g_or(&A.cc->pad[5], (ties ? RF_TIES : 0u) | (viol ? RF_VIOL : 0u));
     if (STG_FILL_STAMPS && rk == STG_FILL_STAMPS_RK && tid == 0) { A.dbg[44] = Wk; A.dbg[45] = P; A.dbg[46] = s1 - s0; A.dbg[47] = fl; }
     LF_STAMP(6);
     LF_STAMP(7);

@@ -138,8 +138,9 @@ union LScanLds {
 static_assert(sizeof(LScanLds) <= 160 * 1024 / 8, "eight scan workgroups per CU");
 
 // Eight waves per SIMD (64 VGPRs) for the plain and error-feedback scans, whose
-// finish (tv16lf2.h) would otherwise set the register budget; the gather
-// scans keep theirs (their finish is the fill launch's).
+// finish (tv16lf2.h) would otherwise set the register budget.  The gather
+// scans run the same in-scan finish but keep the compiler's budget (1 to 8
+// waves per SIMD): their extra streams' loads in flight need the registers.
 template <bool EF, uint32_t NW, uint32_t D, uint32_t GS>
 __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(GS ? 1 : 8, 8))) tv16_lscan(LScanArgs A) {
     __shared__ LScanLds U;
@@ -243,7 +244,7 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(GS
                 st_sc1(reinterpret_cast<uint32_t *>(&A.cp->inc), f2u(A.state->inc));
             }
             tb = f2u(t);
-            wlo = tb > TV16_WIN ? tb - TV16_WIN : 0u;  // window [wlo, tb) just below t
+            wlo = window_lo(tb);  // window [wlo, tb) just below t
             __syncthreads();  // the slot counters are zeroed
         }
         for (uint32_t m0 = 0; m0 < mine; m0 += D) {

@@ -263,8 +263,8 @@ __device__ __noinline__ LeadOut leader(WL &W, const LeadIn I) {
     uint32_t *const go = g, *const gp = go + m, *const op = gp + m;
     uint64_t *const gs = reinterpret_cast<uint64_t *>(g + 4 * (size_t)m);
     const uint32_t *const gs32 = reinterpret_cast<const uint32_t *>(gs);
-    const uint32_t P0 = (uni(I.rem) + 15u) / 16u;
-    const uint32_t sel = min(P0 + 1u, m - 1u);
+    const uint32_t P0 = pops_p0(uni(I.rem));
+    const uint32_t sel = pops_bound(P0, m);
     uint32_t *const hist = W.u.s.hist;
     const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(lk), 0, n * 4u, 0x00020000);
     const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(lc), 0, n * 4u, 0x00020000);
@@ -523,7 +523,7 @@ __device__ __noinline__ LeadOut leader(WL &W, const LeadIn I) {
         if (nlate > LATE_CAP) { O.why = 7; return O; }
         for (uint32_t x = tid; x < nlate; x += FILL_WG) {
             const uint32_t c = late[x];
-            const uint32_t par = (c - 1u) / 2u, sib = ((c - 1u) ^ 1u) + 1u;
+            const uint32_t par = heap_parent(c), sib = heap_sibling(c);
             if (member(par) || (sib < NN && member(sib))) {
                 const uint32_t q = c + 1u, dq = depth_of(q);
                 add_root(dq >= WHL ? (q >> WHL) - 1u : 0u);
@@ -690,8 +690,7 @@ __device__ __noinline__ LeadOut leader(WL &W, const LeadIn I) {
         });
     __syncthreads();
     const uint32_t tr = uni(W.v[12]);
-    uint32_t P = P0;
-    if (tr < P0) P = (uni(I.rem) + (16u - uni(I.tl)) + 15u) / 16u;
+    const uint32_t P = pops_count(uni(I.rem), uni(I.tl), tr);
     if (P > nr) { O.why = 4; return O; }
     // go was stored plain: the order for other workgroups (the crew's
     // emission units) is written through here, sc1 and coalesced
@@ -723,18 +722,7 @@ __device__ __noinline__ LeadOut leader(WL &W, const LeadIn I) {
 // ---------------------------------------------------------------------------
 // the crew
 // ---------------------------------------------------------------------------
-// regime B with lines (or the tail) to fill, and the window does not hold them
-// A ragged tail whose signed sum is NaN joins the reference's heap under a
-// comparator that is then always false: only the literal heap reproduces what
-// make_heap / pop_heap do with it (with 2^m - 1 candidates it climbs from the
-// last leaf to the root and pops first), so every other way declines it.
-__device__ __forceinline__ bool nan_tail(uint32_t flags, uint32_t tail_bits) {
-    return (flags & TV16_DEC_TAIL) && (tail_bits & 0x7fffffffu) > 0x7f800000u;
-}
-__device__ __forceinline__ bool crew_wants(uint32_t flags, uint32_t M, uint32_t mode, uint32_t tail_bits) {
-    return (flags & TV16_DEC_B) && (M || (flags & TV16_DEC_TAIL)) && (!(flags & TV16_DEC_WIN) || mode == 4u) &&
-           mode != 2u && !nan_tail(flags, tail_bits);  // mode 2 (tests): the literal heap for every regime-B bucket
-}
+// (which buckets it takes: tv16_finish.h crew_wants)
 
 // scratch layout of a crew bucket (words of d.heap: 2 (nb + 64) of them)
 struct CrewMap {
@@ -844,7 +832,7 @@ __device__ __noinline__ bool crew_c(WL &W, const CrewBk &B, CrewCtl *ctl, uint32
     __syncthreads();
     uint32_t beta, r1;
     {   // descending bins, 16 per thread
-        const uint32_t P0 = (B.rem + 15u) / 16u, sel = min(P0 + 1u, B.N - 1u);
+        const uint32_t sel = pops_bound(pops_p0(B.rem), B.N);
         constexpr uint32_t PER = WBINS / FILL_WG;
         uint32_t hc[PER], s = 0;
 #pragma unroll
@@ -1092,19 +1080,19 @@ __device__ __forceinline__ void crew_from_decisions(WideLds &W, FillLds &S, cons
         for (uint32_t b = 0; b < A.nbk && !failed; ++b) {
             const Decision &Dc = A.dec[b];
             const uint64_t w0 = ld_sc1(&Dc.w[0]);
-            if ((uint32_t)(w0 >> 32) != ((A.epoch << 8) | TV16_TAG_DEC)) continue;
+            if (dec_hi(w0) != decision_tag(A.epoch)) continue;
             const uint64_t w1 = ld_sc1(&Dc.w[1]), w2 = ld_sc1(&Dc.w[2]), w3 = ld_sc1(&Dc.w[3]);
-            const uint32_t flags = (uint32_t)w0;
-            if (!crew_wants(flags, (uint32_t)w1, A.mode, (uint32_t)w2)) continue;
+            const DecisionView v = decision_unpack(w0, w1, w2, w3, A.bk[b].nb, A.bk[b].dst_len);
+            if (!crew_wants(v.flags, v.M, A.mode, v.tail_bits)) continue;
             CrewBk &B = W.bk[nr++];
             B.d = A.bk[b];
             B.slot = b;
-            B.cnt = (uint32_t)(w1 >> 32);
-            B.rem = B.d.dst_len - B.cnt;
-            B.tail = (flags & TV16_DEC_TAIL) ? 1u : 0u;
-            B.N = B.d.nb - (uint32_t)(w3 >> 32) + B.tail;
-            B.tbits = (uint32_t)w3;
-            B.tail_bits = (uint32_t)w2;
+            B.cnt = v.cnt;
+            B.rem = v.rem;
+            B.tail = v.tail ? 1u : 0u;
+            B.N = v.N;
+            B.tbits = v.t_bits;
+            B.tail_bits = v.tail_bits;
         }
         W.nreq = nr;
     }
@@ -1119,9 +1107,7 @@ __device__ __forceinline__ void crew_from_decisions(WideLds &W, FillLds &S, cons
 __device__ __forceinline__ void crew_lfin(LfinLds &Lf, const Tv16FillArgs &A) {
     LfinDec D;
     lfin_prefix(Lf, Lf.args, D);
-    const uint32_t flags =
-        D.regimeB ? (TV16_DEC_B | (D.tail_cand ? TV16_DEC_TAIL : 0u) | (D.listw ? TV16_DEC_WIN : 0u)) : 0u;
-    const bool want = crew_wants(flags, D.M, A.mode, f2u(D.tail_key)) && !ld_sc1(A.fail);
+    const bool want = crew_wants(decision_flags(D), D.M, A.mode, f2u(D.tail_key)) && !ld_sc1(A.fail);
     __syncthreads();  // every read of the lfin view is done
     WideLdsBig &W = *reinterpret_cast<WideLdsBig *>(&Lf);
     if (threadIdx.x == 0) {

@@ -5,12 +5,11 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "tv16_const.h"  // CAND_CAP, TV16_WIN, the Decision flags and tag
 
 namespace stg {
 
-constexpr uint32_t CAND_CAP = 8192;          // regime-B window entries per bucket (+1 for the ragged tail)
 constexpr uint32_t CAND_WORDS = 4 * CAND_CAP; // per bucket: line-sum bits | line position | candidate index | spare
-constexpr uint32_t TV16_WIN = 1u << 18;      // regime-B window below t, in ulps of t (~3.1 %)
 constexpr uint32_t TV16_SCAN_LDS = 35584;     // LDS bytes of a scan workgroup (bound; tv16.hip checks)
 
 constexpr uint32_t TV_TILE = 8192;           // top-k elements per tile (32 KiB)
@@ -42,10 +41,8 @@ struct CallCtl {
 // chunk: [1..3] first, drained, then [0] = {tag:32 | flags:32}; read by the
 // follow-on fill launch.
 struct alignas(32) Decision {
-    uint64_t w[4];      // [1] = {cnt:32 | M:32}, [2] = {Wtot:32 | tail key bits:32}, [3] = {Qtot:32 | t bits:32}
+    uint64_t w[4];      // packed and unpacked by tv16_finish.h (decision_pack, decision_unpack)
 };
-constexpr uint32_t TV16_DEC_B = 1, TV16_DEC_WIN = 2, TV16_DEC_TAIL = 4;  // Decision flags
-constexpr uint32_t TV16_TAG_DEC = 3;
 constexpr uint32_t POISON_COUNT = 0xffffffffu;  // *count_out of a launch that hit a device failure
 struct FillCtl {
     CallCtl cc[2];                     // [epoch parity]
