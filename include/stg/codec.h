@@ -194,7 +194,23 @@ typedef struct stg_send_task {
  * and writes the wire form.  A single task of 2^22..2^24 elements keeps the
  * one-bucket scan with the sources summed inside its streaming pass.  Staging
  * takes 8 bytes per idx_cap slot of the call, kept with the workspace.
- *   thresholdv16 only (STG_ERR_UNSUPPORTED for the other codecs).
+ *   thresholdv16 and threshold-v (STG_ERR_UNSUPPORTED for top-k).
+ *   A threshold-v handle ("thresholdv"): the key is the pointer bucket.d_src
+ * (thresholdv.cpp:44; `key` and idx_offset are ignored, and a key occurs twice
+ * when two tasks with n > 0 share that pointer).  Its count varies, *d_count =
+ * min(qualifiers, idx_cap), while the engine sends all W = min(idx_cap, n)
+ * slots, the unused ones holding (index 0, value 0.0) (compress.cpp:60-64): the
+ * first *d_count wire slots are the pairs, slots [*d_count, W) the wire form
+ * of (0, 0.0f), the block / tail split at 8 * ((W - 1) / 8), nothing past W
+ * written; under error feedback grad and residual are zeroed at the true
+ * index of all W slots -- element 0 whenever *d_count < W -- and the residual
+ * ends equal to grad[0].  That is step 1 above into zeroed temporaries and
+ * step 2 with count = W.  Launches: the gather launches as above; per key's
+ * first call its first-threshold select; then one scan launch per 16 tasks
+ * (tv_batch.hip: a task takes max(1, ceil(n / 4 / 4096)) workgroups, a launch
+ * also closes before min(2048, CUs) of them, a larger task runs alone through
+ * the per-tensor scan and a copy to the residual), the residual copy fused;
+ * then one finishing launch per 16 tasks (stg_debug_tv_batch_plan).
  *   All or nothing: every task is checked before any device call or key-state
  * change, and stg_last_error() names the offending task index.
  * STG_ERR_INVALID: a null handle, a null `tasks` with ntasks > 0, the
@@ -613,6 +629,15 @@ int stg_param_publish_batch_device(const stg_publish_task_t *tasks, size_t ntask
  * a null array with ntasks > 0 or num_cu < 1). */
 int stg_debug_publish_launches(const uint32_t *idx_caps, size_t ntasks, int num_cu);
 
+/* Diagnostics, plain host arithmetic (no device): the scan launches a
+ * threshold-v stg_merge_send_batch_device call makes for tasks of n[i] floats
+ * on a device of num_cu compute units.  launch_of[i]: the launch of task i
+ * (0xffffffff for n[i] == 0: none); first_range[i]: its first workgroup
+ * there (0 for a task that runs alone).  Returns the launch count, or
+ * STG_ERR_INVALID for a null array with ntasks > 0 or num_cu < 1. */
+int stg_debug_tv_batch_plan(const uint64_t *n, size_t ntasks, int num_cu, uint32_t *first_range,
+                            uint32_t *launch_of);
+
 /* Gather-add from bf16 / fp16 gradient sources.  The node's other GPUs may
  * hold 16-bit model replicas (stg_param_publish_batch_device keeps them
  * current) and so produce 16-bit gradients; these entry points read them as
@@ -643,7 +668,7 @@ typedef struct stg_grad_src {
  *   stg_merge_send_batch_typed_device: srcs[i] is null -- task i then uses its
  * fp32 d_grads exactly as stg_merge_send_batch_device -- or a host array of
  * tasks[i].num_gpus typed sources, and tasks[i].d_grads is ignored (with
- * num_gpus == 1 the array holds only term0).  thresholdv16 only.
+ * num_gpus == 1 the array holds only term0).  thresholdv16 and threshold-v.
  *   Routing: a call whose sources are all fp32 and in place runs the fp32
  * entry point's launches.  Otherwise 16-bit sources load 16 (or 8) bytes per
  * lane and fp32 streams 16, in lane groups of 8 (or 4) elements, wherever one

@@ -308,7 +308,18 @@ class Compressor:
         pairs.  ``dst_idx`` is int16 under flag 1 (else int32), ``dst_val``
         int16-typed fp16 bits under flag 2 (else float32); ``dst_idx.numel()``
         is the pair capacity.  Keys must be distinct within a call.
-        thresholdv16 only.  ``items`` may be a prebuilt ``SendTasks``; an item
+        thresholdv16 and threshold-v (top-k: ``CodecError``, unsupported).
+        On a ``ThresholdvCompressor`` the key is the pointer of the bucket
+        (``key`` is ignored) and the count varies, ``min(qualifiers,
+        dst_idx.numel())``, while the engine sends all ``W =
+        min(dst_idx.numel(), n)`` slots (compress.cpp:60-64): the first
+        ``count`` wire slots are the pairs, slots ``[count, W)`` the wire form
+        of ``(0, 0.0)``, the block / tail split of the packing at ``8 * ((W -
+        1) // 8)``, nothing past ``W`` written; with ``residual``, grad and
+        residual are zeroed at the true index of all ``W`` slots -- element 0
+        whenever ``count < W``.  That is ``merge_gather_compress_async`` into
+        zeroed temporaries, then ``wire_encode`` of their first ``W`` slots.
+        ``items`` may be a prebuilt ``SendTasks``; an item
         may carry bfloat16 / float16 gradients and a trailing ``bucket`` as
         described there (``stg_merge_send_batch_typed_device``).  Returns
         the int32 counts tensor (no host sync)."""

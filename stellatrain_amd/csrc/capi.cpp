@@ -770,6 +770,98 @@ int publish_pack(size_t ntasks, int num_cu, Cap cap, Fill fill, Launch launch) {
 // low address bits that must be clear for a replica of this STG_DT_* type
 uintptr_t publish_elem_mask(int dtype) { return dtype == STG_DT_F32 ? 3u : 1u; }
 
+// The scan launches of a threshold-v send call (tv_batch.hip), by the one rule
+// the entry point and stg_debug_tv_batch_plan share: task i of n(i) > 0 floats
+// takes tv_batch_ranges(n) ranges of a table that closes at SEND_BATCH tasks or
+// before tv_batch_range_cap(num_cu) ranges; a task with more ranges than the
+// cap runs alone(i) -- the pending table is launched first, so the launches
+// keep the tasks' order.  fill(i, item) writes the item (blk0 and ranges are
+// set), launch(table, ranges) enqueues it.
+template <class N, class Fill, class Launch, class Alone>
+int tv_batch_pack(size_t ntasks, int num_cu, N n, Fill fill, Launch launch, Alone alone) {
+    const uint64_t cap = stg::tv_batch_range_cap(num_cu);
+    auto pk = stg::make_packer<stg::TvBatch>(cap, launch);
+    for (size_t i = 0; i < ntasks; ++i) {
+        const uint64_t ni = n(i);
+        if (!ni) continue;
+        const uint64_t ranges = stg::tv_batch_ranges(ni);
+        if (ranges > cap) {
+            if (const int rc = pk.flush()) return rc;
+            if (const int rc = alone(i)) return rc;
+            continue;
+        }
+        stg::TvBatchTask *d;
+        if (const int rc = pk.add(ranges, &d)) return rc;
+        d->ranges = (uint32_t)ranges;
+        fill(i, d);
+    }
+    return pk.flush();
+}
+
+// The threshold-v scans of a send call, after its gather launches: bk[i] is
+// task i's bucket with d_idx / d_val pointing into the staging, res[i] its
+// residual (the scan copies the gathered bucket to it) or null.
+int run_tv_send(stg_codec *h, Workspace *ws, const stg_bucket_t *bk, float *const *res, size_t ntasks, hipStream_t s) {
+    std::lock_guard<std::mutex> g(ws->mu);
+    int rc;
+    // range words (tv.hip): counts at tile_cnt, maxima at tile_aux, two words per range (zeroed when fresh)
+    if ((rc = ws->ensure(1, 2 * (size_t)stg::TV_MAXG, 1, true))) return rc;
+    std::vector<KeyState *> st(ntasks, nullptr);
+    std::vector<char> fresh(ntasks, 0);
+    const uint64_t cap = stg::tv_batch_range_cap(h->num_cu);
+    for (size_t i = 0; i < ntasks; ++i) {
+        const stg_bucket_t &b = bk[i];
+        if (!b.n) {
+            HIP_TRY(hipMemsetAsync(b.d_count, 0, sizeof(uint32_t), s));
+            continue;
+        }
+        bool f;
+        if ((rc = h->slot(state_key(h->method, b.key, b.d_src), &st[i], &f))) return rc;
+        fresh[i] = f;
+        // a key's first call: its threshold from the gathered bucket, ahead of
+        // the scan launch (a task that runs alone: inside launch_tv)
+        if (f && stg::tv_batch_ranges(b.n) <= cap)
+            HIP_TRY(stg::launch_tv_first(b.d_src, b.n, b.k, st[i], ws->d, h->num_cu, s));
+    }
+    auto next_tag = [ws] {
+        if (++ws->tv_tag == 0) ws->tv_tag = 1;
+        return ws->tv_tag;
+    };
+    return tv_batch_pack(
+        ntasks, h->num_cu, [&](size_t i) { return (uint64_t)bk[i].n; },
+        [&](size_t i, stg::TvBatchTask *d) {
+            const stg_bucket_t &b = bk[i];
+            d->src = b.d_src;
+            d->resid = res[i];
+            d->idx = b.d_idx;
+            d->val = b.d_val;
+            d->count_out = b.d_count;
+            d->state = st[i];
+            d->n = b.n;
+            d->k = b.k;
+            d->cap = (uint32_t)b.idx_cap;
+        },
+        [&](stg::TvBatch &w, uint32_t ranges) -> int {
+            w.tag = next_tag();
+            w.base = ws->tv_base;
+            HIP_TRY(stg::launch_tv_batch(w, ranges, ws->d, s));
+            ws->tv_base += ranges;
+            return STG_OK;
+        },
+        [&](size_t i) -> int {
+            const stg_bucket_t &b = bk[i];
+            uint32_t grid = 0;
+            stg::TvLaunch a{b.d_src, b.n, b.k, (uint32_t)b.idx_cap, b.d_idx, b.d_val, b.d_count, st[i],
+                            fresh[i] != 0, h->num_cu, nullptr, next_tag(), ws->tv_base, &grid};
+            HIP_TRY(stg::launch_tv(a, ws->d, s));
+            ws->tv_base += grid;
+            // (tv_pass does not write the residual: the copy pass of the per-tensor sequence)
+            if (res[i])
+                HIP_TRY(hipMemcpyAsync(res[i], b.d_src, b.n * sizeof(float), hipMemcpyDeviceToDevice, s));
+            return STG_OK;
+        });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1010,8 +1102,8 @@ static int send_batch(stg_codec_t h, const stg_send_task_t *tasks, const stg_gra
     CritPath crit_path;
     if (!h) return fail(STG_ERR_INVALID, "null codec handle");
     if (ntasks && !tasks) return fail(STG_ERR_INVALID, "null task array");
-    if (h->method != M_TV16)
-        return fail(STG_ERR_UNSUPPORTED, "the one-call send path scans with thresholdv16 only "
+    if (h->method != M_TV16 && h->method != M_TV)
+        return fail(STG_ERR_UNSUPPORTED, "the one-call send path scans with thresholdv16 or thresholdv only "
                                          "(gather-compress, then stg_wire_encode_device)");
     // all or nothing: every task is checked before any device call or key state exists
     auto tfail = [](size_t i, int code, const std::string &msg) {
@@ -1048,6 +1140,7 @@ static int send_batch(stg_codec_t h, const stg_send_task_t *tasks, const stg_gra
             ++live;
             one = i;
         }
+        if (h->method == M_TV && !b.n) continue;  // (keyed by the bucket's pointer: an empty task has no key)
         const auto ins = seen.emplace(state_key(h->method, b.key, b.d_src), i);
         if (!ins.second)
             return tfail(i, STG_ERR_INVALID, "key repeats task " + std::to_string(ins.first->second) +
@@ -1089,7 +1182,14 @@ static int send_batch(stg_codec_t h, const stg_send_task_t *tasks, const stg_gra
     // own streaming pass (tv16lone.hip), one pass over the bucket instead of two.
     // That pass reads fp32 sources only: with a 16-bit source or a typed first
     // term the typed gather-add runs first, then the plain scan (the same bits).
-    const bool lone = live == 1 && tasks[one].bucket.n >= (size_t(1) << 22) && tasks[one].bucket.n <= (size_t(1) << 24);
+    // (thresholdv16's: a threshold-v task always takes the gather launches below)
+    const bool tv = h->method == M_TV;
+    const bool lone = !tv && live == 1 && tasks[one].bucket.n >= (size_t(1) << 22) &&
+                      tasks[one].bucket.n <= (size_t(1) << 24);
+    // the scans of the call, after its gather launches
+    auto scan = [&]() {
+        return tv ? run_tv_send(h, ws, bk.data(), res.data(), ntasks, s) : run_tv16(h, bk.data(), ntasks, s, res.data());
+    };
     if (lone && any_typed) {
         HIP_TRY(stg::launch_gather_add_typed(gather_of(one), 0, tasks[one].bucket.n, h->num_cu, s));
         if ((rc = run_tv16(h, bk.data(), ntasks, s, res.data()))) return rc;
@@ -1117,7 +1217,7 @@ static int send_batch(stg_codec_t h, const stg_send_task_t *tasks, const stg_gra
             d->dtypes = g.dtypes;
         }
         if ((rc = gb.flush())) return rc;
-        if ((rc = run_tv16(h, bk.data(), ntasks, s, res.data()))) return rc;
+        if ((rc = scan())) return rc;
     } else {
         // gather groups: a launch closes at SEND_BATCH tasks or before its grid
         // would pass num_cu * 8 workgroups (a larger tensor runs alone)
@@ -1147,7 +1247,29 @@ static int send_batch(stg_codec_t h, const stg_send_task_t *tasks, const stg_gra
             d->head = (uint32_t)head;
         }
         if ((rc = gb.flush())) return rc;
-        if ((rc = run_tv16(h, bk.data(), ntasks, s, res.data()))) return rc;
+        if ((rc = scan())) return rc;
+    }
+    if (tv) {
+        // finish groups: every slot's wire form by the device count, error feedback by the true indices
+        auto fd = stream_packer<stg::SendFinishDcBatch>(GRID_MAX, stg::launch_ef_pack_batch_dc, s);
+        for (size_t i = 0; i < ntasks; ++i) {
+            const stg_bucket_t &b = tasks[i].bucket;
+            const size_t slots = std::min<size_t>(b.idx_cap, b.n);  // the slots the engine sends
+            if (!slots) continue;
+            stg::SendFinishDc *d;
+            if ((rc = fd.add((slots + STG_WG - 1) / STG_WG, &d))) return rc;
+            d->idx = bk[i].d_idx;
+            d->val = bk[i].d_val;
+            d->count = b.d_count;
+            d->idx_out = b.d_idx;
+            d->val_out = b.d_val;
+            d->grad = const_cast<float *>(b.d_src);
+            d->resid = tasks[i].d_residual;
+            d->n = b.n;
+            d->slots = (uint32_t)slots;
+            d->flag = (uint32_t)tasks[i].wire_flag;
+        }
+        return fd.flush();
     }
     // finish groups: tail copy, error feedback by the true indices, wire form
     auto fb = stream_packer<stg::SendFinishBatch>(GRID_MAX, stg::launch_ef_pack_batch, s);
@@ -2339,6 +2461,30 @@ int stg_debug_publish_launches(const uint32_t *idx_caps, size_t ntasks, int num_
         ntasks, num_cu, [&](size_t i) { return idx_caps[i]; }, [](size_t, stg::PublishTask *) {},
         [&](stg::PublishBatch &, uint32_t) -> int {
             ++launches;
+            return STG_OK;
+        });
+    return launches;
+}
+
+int stg_debug_tv_batch_plan(const uint64_t *n, size_t ntasks, int num_cu, uint32_t *first_range, uint32_t *launch_of) {
+    if ((ntasks && (!n || !first_range || !launch_of)) || num_cu < 1) return STG_ERR_INVALID;
+    int launches = 0;
+    for (size_t i = 0; i < ntasks; ++i) {
+        first_range[i] = 0;
+        launch_of[i] = 0xffffffffu;  // (an empty task: no launch)
+    }
+    tv_batch_pack(
+        ntasks, num_cu, [&](size_t i) { return n[i]; },
+        [&](size_t i, stg::TvBatchTask *d) {
+            first_range[i] = d->blk0;
+            launch_of[i] = (uint32_t)launches;
+        },
+        [&](stg::TvBatch &, uint32_t) -> int {
+            ++launches;
+            return STG_OK;
+        },
+        [&](size_t i) -> int {
+            launch_of[i] = (uint32_t)launches++;
             return STG_OK;
         });
     return launches;

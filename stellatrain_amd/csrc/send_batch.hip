@@ -12,8 +12,12 @@
 //   (the thresholdv16 scans, unchanged, into u32 / f32 staging; residual copy fused)
 //   ef_pack_batch    : ragged tail -> residual, zero the selected entries by
 //                      their TRUE indices, write the wire form of every pair
+// On a threshold-v handle the scans are tv_batch.hip's (residual copy fused
+// there too) and the finish is
+//   ef_pack_batch_dc : the pair count read from the device; all min(idx_cap,
+//                      n) slots written, the unused ones as (0, 0.0f)
 // Workgroups are dealt to the tensors by host-computed first-workgroup offsets
-// (blk0), as in wire_encode_batch.  Both kernels are plain streaming code:
+// (blk0), as in wire_encode_batch.  These kernels are plain streaming code:
 // nothing waits on another workgroup and no LDS is used.
 //
 // Bounds.  gather_add_batch: HBM (xGMI for peer sources), 4 (dst) + 4
@@ -173,7 +177,43 @@ __global__ void __launch_bounds__(STG_WG) ef_pack_batch(SendFinishBatch w) {
     }
 }
 
+// The finish of a threshold-v task (tv_batch.hip's scan, or tv_pass for a task
+// that ran alone): the pair count is the task's device word.  The engine sends
+// all W = min(idx_cap, n) slots, the unused ones holding (index 0, value 0.0)
+// (compress.cpp:60-64): lane j < W writes the wire form of staged pair j when
+// j < count and of (0, 0.0f) otherwise, by position against wend = 8 * ((W -
+// 1) / 8); under error feedback it zeroes grad and residual at the pair's true
+// index, and at element 0 for an unused slot (compress.cpp:178-179).  A
+// poisoned count writes nothing and zeroes nothing.  The scan copied the whole
+// bucket to the residual, so every element is only ever written (zeros) here:
+// no ragged-tail case, no order between workgroups.
+__global__ void __launch_bounds__(STG_WG) ef_pack_batch_dc(SendFinishDcBatch w) {
+    const SendFinishDc &d = w.t[batch_item(w.t, w.nt)];
+    const uint32_t wb = blockIdx.x - d.blk0;
+    const size_t j = (size_t)wb * STG_WG + threadIdx.x;
+    const uint32_t count = *d.count;
+    if (count == POISON_COUNT || j >= d.slots) return;
+    const size_t wend = 8 * ((size_t)(d.slots - 1) / 8);
+    const bool pair = j < count;
+    const uint32_t ix = pair ? d.idx[j] : 0u;
+    const float v = pair ? d.val[j] : 0.f;
+    if (d.flag & 1u) static_cast<uint16_t *>(d.idx_out)[j] = (uint16_t)wire_idx16(ix, j, wend);
+    else static_cast<uint32_t *>(d.idx_out)[j] = ix;
+    if (d.flag & 2u) static_cast<uint16_t *>(d.val_out)[j] = (uint16_t)wire_val16(v, j, wend);
+    else static_cast<float *>(d.val_out)[j] = v;
+    if (d.resid && ix < d.n && (pair || j == count)) {  // (one lane of the unused slots zeroes element 0)
+        d.grad[ix] = 0.f;
+        d.resid[ix] = 0.f;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_ef_pack_batch_dc(const SendFinishDcBatch &w, uint32_t blocks, hipStream_t s) {
+    if (!w.nt || !blocks) return hipSuccess;
+    ef_pack_batch_dc<<<blocks, STG_WG, 0, s>>>(w);
+    return hipGetLastError();
+}
 
 hipError_t launch_gather_add_batch(const SendGatherBatch &w, uint32_t blocks, hipStream_t s) {
     if (!w.nt || !blocks) return hipSuccess;

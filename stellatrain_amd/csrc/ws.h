@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "common.h"
 #include "tv16_const.h"  // CAND_CAP, TV16_WIN, the Decision flags and tag
 
@@ -640,6 +642,63 @@ struct SendFinishBatch {
 };
 static_assert(sizeof(SendFinishBatch) <= 2048, "kernel arguments: stay well under 4 KiB");
 hipError_t launch_ef_pack_batch(const SendFinishBatch &w, uint32_t blocks, hipStream_t s);
+// The same path for threshold-v (tv_batch.hip, send_batch.hip): one scan launch
+// for up to SEND_BATCH tasks, then a finish that reads each task's pair count
+// from the device.
+//
+// The scan's ranges (1024-thread workgroups, as tv_pass's): a task of n floats
+// takes tv_batch_ranges(n), each of at most TV_BATCH_RANGE float4; a launch
+// closes at SEND_BATCH tasks or before its ranges would pass
+// tv_batch_range_cap(num_cu); a task with more ranges than that runs alone
+// through launch_tv.
+constexpr uint32_t TV_BATCH_RANGE = 4096;  // float4 per range at most (64 KiB)
+inline uint64_t tv_batch_ranges(uint64_t n) {
+    return std::max<uint64_t>(1, (n / 4 + TV_BATCH_RANGE - 1) / TV_BATCH_RANGE);
+}
+inline uint64_t tv_batch_range_cap(int num_cu) {
+    return std::max<uint64_t>(1, std::min<uint64_t>(TV_MAXG, (uint64_t)std::max(num_cu, 1)));
+}
+struct TvBatchTask {
+    const float *src;              // the gathered grad[0]
+    float *resid;                  // receives every element of src (null: no error feedback)
+    uint32_t *idx;                 // staged pairs: positions ...
+    float *val;                    // ... and values, cap of each
+    uint32_t *count_out;
+    KeyState *state;
+    uint64_t n;
+    uint32_t k, cap;
+    uint32_t blk0;                 // the task's first range (ticket) in the launch
+    uint32_t ranges;               // tv_batch_ranges(n)
+};
+struct TvBatch {
+    TvBatchTask t[SEND_BATCH];
+    uint32_t nt;
+    uint32_t tag;                  // the launch's tag (>= 1) on every range word, from the workspace's tv_pass sequence
+    uint64_t base;                 // ws.tv_ticket's value when the launch starts (it advances by the launch's ranges)
+};
+static_assert(sizeof(TvBatch) <= 2048, "kernel arguments: stay well under 4 KiB");
+// ranges = the sum of the tasks' ranges <= tv_batch_range_cap; the range words
+// are ws.tile_cnt / ws.tile_aux (TV_MAXG pairs, zero when fresh), as launch_tv's
+hipError_t launch_tv_batch(const TvBatch &w, uint32_t ranges, const DevWS &ws, hipStream_t s);
+// a key's first threshold from its gathered bucket (tv.hip's, ahead of the scan launch)
+hipError_t launch_tv_first(const float *src, size_t n, uint32_t k, KeyState *state, const DevWS &ws, int num_cu,
+                           hipStream_t s);
+struct SendFinishDc {
+    const uint32_t *idx;           // the scan's staged pairs, *count of them valid
+    const float *val;
+    const uint32_t *count;         // the task's device count (POISON_COUNT: nothing is written)
+    void *idx_out, *val_out;       // the task's wire-form outputs, typed by flag
+    float *grad, *resid;           // error feedback (resid null: pack only)
+    uint64_t n;
+    uint32_t slots;                // W = min(idx_cap, n): all of them are written
+    uint32_t flag, blk0;
+};
+struct SendFinishDcBatch {
+    SendFinishDc t[SEND_BATCH];
+    uint32_t nt;
+};
+static_assert(sizeof(SendFinishDcBatch) <= 2048, "kernel arguments: stay well under 4 KiB");
+hipError_t launch_ef_pack_batch_dc(const SendFinishDcBatch &w, uint32_t blocks, hipStream_t s);
 // Publishing a step's changed parameters to the node's model replicas
 // (publish.hip): replica[j] = cvt(param[j]) at the indices of the step's
 // merged stream, for up to PUBLISH_BATCH tasks per launch.  The table --

@@ -143,7 +143,12 @@ class CodecEngine:
         item may be ``(key, grads, residual, bucket)``: ``grads`` of float32,
         bfloat16 or float16 and ``bucket`` the float32 tensor that receives the
         sum, as ``SendTasks`` describes (without ``bucket``, ``grads[1:]`` may
-        still be 16-bit)."""
+        still be 16-bit).  Works under ``configure_compression("thresholdv")``
+        as well: the key is then the bucket's pointer, the count varies, and
+        all ``W = min(numel, n)`` slots are written -- the pairs, then the wire
+        form of ``(0, 0.0)`` -- with element 0 zeroed by the error feedback
+        whenever the count is below ``W``
+        (``Compressor.merge_send_batch_async``)."""
         import torch
         send, streams = [], []
         for it in items:

@@ -20,6 +20,8 @@ times the other configs on one GPU and prints one JSON line per measurement:
   WMERGE  merge_optimize straight from wire-form rank streams against one
       wire_decode per rank plus the decoded call (60,000 floats and 64 MiB);
   BMERGE  merge_optimize_batch over 256 tensors against the per-tensor loop;
+  TVSEND  (--only tvsend) the one-call send path on a threshold-v handle over
+      256 tensors against the per-tensor loop, three rotated cycles;
   E2E thresholdv16 64 MiB host-inclusive (serial and overlapped).
 
 Every device timing rotates over >= 512 MB of distinct buckets so the 256 MB
@@ -554,6 +556,29 @@ def send16(torch, calls):
     return out
 
 
+def tvsend(torch, iters=21):
+    """The one-call send path on a threshold-v handle (tools/send_bench.py's
+    sets and timing: 256 tensors of 60,000 floats, and the first 256 C4 sizes;
+    N = 2, the residual carried, flag by wire_flag) against the per-tensor
+    loop on the same build, the loop repeated as a control: three cycles, the
+    ways' order within a round rotated from cycle to cycle."""
+    import send_bench
+    from stellatrain_amd.shard import c4_sizes
+    ways = ["loop", "batch", "prebuilt", "loop_control"]
+    out = []
+    for cycle in range(3):
+        order = ways[cycle:] + ways[:cycle]
+        for label, sizes, nsets in (("256 tensors of 60,000 floats", [60000] * 256, 4),
+                                    ("first 256 sizes of the C4 list", c4_sizes()[:256], 2)):
+            row = send_bench.measure(torch, label, sizes, nsets, set(ways), 3, iters, "thresholdv", order)
+            row.update(cycle=cycle, order=order,
+                       control_spread_ms=round(max(row["loop_ms_min_max"][1], row["loop_control_ms_min_max"][1]) -
+                                               min(row["loop_ms_min_max"][0], row["loop_control_ms_min_max"][0]), 4))
+            out.append(row)
+            torch.cuda.empty_cache()
+    return out
+
+
 def gather_fused(torch, calls):
     """One MERGE task with the intra-node gather ahead of it on a 64 MiB
     bucket (cpu_gather.cpp:59-87 then compress.cpp:139-186):
@@ -894,6 +919,9 @@ def main():
             emit(d)
     if "send16" in only:
         for d in send16(torch, a.calls):
+            emit(d)
+    if "tvsend" in only:
+        for d in tvsend(torch):
             emit(d)
     if "ef" in only:
         for d in merge_ef(torch, max(8, a.calls // 4)):

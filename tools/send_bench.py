@@ -16,6 +16,8 @@ The ways alternate within every round and each has a codec handle of its own;
 the median of --iters rounds after --warmup is reported, one JSON line per set.
 
   --only loop       runs on a tree without the batched call (the parent commit)
+  --codec thresholdv  the same on a threshold-v handle (its loop zeroes the
+                    temporaries first: the engine sends every slot)
   --trace WAY       for a kernel trace run: warm up the 60,000-float set, then
                     one iteration of WAY between two stg_synth_fill_device
                     launches of 1 float (the only synth kernels of the run)
@@ -57,26 +59,35 @@ def build_sets(torch, sizes, nsets, dev):
     return sets
 
 
-def ways_for(torch, sets, only):
+def ways_for(torch, sets, only, codec="thresholdv16"):
     import stellatrain_amd as S
     ways = {}
-    if "loop" in only:
-        comp = S.ThresholdvCompressor16()
+    make = lambda: S.make_compressor(codec)  # noqa: E731
+    # threshold-v's count varies and the engine sends every slot, the unused
+    # ones zero (compress.cpp:60-64): its loop zeroes the temporaries first
+    # (torch._foreach_zero_; it may still run as one fill per tensor)
+    temps = [[t["ti"] for t in ts] + [t["tv"] for t in ts] for ts in sets] if codec == "thresholdv" else None
+    for name in ("loop", "loop_control"):  # loop_control: the loop again, on a handle of its own
+        if name not in only:
+            continue
+        comp = make()
         cnts = [torch.zeros(len(ts), dtype=torch.int32, device=ts[0]["r"].device) for ts in sets]
 
-        def loop(si, comp=comp):
+        def loop(si, comp=comp, cnts=cnts):
             ts = sets[si]
+            if temps:
+                torch._foreach_zero_(temps[si])
             for j, t in enumerate(ts):
                 comp.merge_gather_compress_async(t["key"], t["g"], t["k"], t["ti"], t["tv"], residual=t["r"],
                                                  count=cnts[si][j:j + 1])
             S.wire_encode_batch([(t["ti"], t["tv"], t["flag"], t["di"], t["dv"]) for t in ts])
-        ways["loop"] = (loop, comp)
+        ways[name] = (loop, comp)
     items = [[(t["key"], t["g"], t["k"], t["di"], t["dv"], t["r"], t["flag"]) for t in ts] for ts in sets]
     if "batch" in only:
-        comp_b = S.ThresholdvCompressor16()
+        comp_b = make()
         ways["batch"] = (lambda si: comp_b.merge_send_batch_async(items[si]), comp_b)
     if "prebuilt" in only:
-        comp_p = S.ThresholdvCompressor16()
+        comp_p = make()
         pre = [S.SendTasks(it) for it in items]
         ways["prebuilt"] = (lambda si: comp_p.merge_send_batch_async(pre[si]), comp_p)
     return ways
@@ -87,10 +98,13 @@ def refill(ts):
         t["g"][0].copy_(t["fresh"])
 
 
-def measure(torch, label, sizes, nsets, only, warmup, iters):
+def measure(torch, label, sizes, nsets, only, warmup, iters, codec="thresholdv16", order=None):
+    """order: the ways in the order a round runs them (default: as built)."""
     dev = torch.device("cuda", 0)
     sets = build_sets(torch, sizes, nsets, dev)
-    ways = ways_for(torch, sets, only)
+    ways = ways_for(torch, sets, only, codec)
+    if order:
+        ways = {w: ways[w] for w in order}
     t = {w: [] for w in ways}
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     turn = 0
@@ -106,7 +120,8 @@ def measure(torch, label, sizes, nsets, only, warmup, iters):
             torch.cuda.synchronize()
             if r >= warmup:
                 t[w].append(e0.elapsed_time(e1))
-    row = {"config": f"SEND one iteration's sender side, {label}, N=2, k=1%, residual carried", "tensors": len(sizes),
+    row = {"config": f"SEND one iteration's sender side, {label}, N=2, k=1%, residual carried"
+                     + ("" if codec == "thresholdv16" else f", {codec}"), "tensors": len(sizes),
            "floats": int(sum(sizes)), "buffer_sets": nsets, "warmup": warmup, "iters": iters}
     for w, (_, comp) in ways.items():
         comp.check_device()
@@ -114,16 +129,16 @@ def measure(torch, label, sizes, nsets, only, warmup, iters):
         row[f"{w}_ms_min_max"] = [round(min(t[w]), 4), round(max(t[w]), 4)]
     if "loop" in t:
         for w in t:
-            if w != "loop":
+            if w not in ("loop", "loop_control"):
                 row[f"loop_over_{w}"] = round(row["loop_ms"] / row[f"{w}_ms"], 2)
     return row
 
 
-def trace(torch, way):
+def trace(torch, way, codec="thresholdv16"):
     from stellatrain_amd._capi import check, lib
     dev = torch.device("cuda", 0)
     sets = build_sets(torch, [60000] * 256, 1, dev)
-    fn, comp = ways_for(torch, sets, {way})[way]
+    fn, comp = ways_for(torch, sets, {way}, codec)[way]
     mark = torch.zeros(1, dtype=torch.float32, device=dev)
     sp = C.c_void_p(torch.cuda.current_stream(0).cuda_stream)
     for _ in range(4):
@@ -161,6 +176,7 @@ def main():
     p.add_argument("--trace", default=None)
     p.add_argument("--count-trace", default=None)
     p.add_argument("--tag", default="")
+    p.add_argument("--codec", default="thresholdv16", choices=["thresholdv16", "thresholdv"])
     a = p.parse_args()
     if a.count_trace:
         print(json.dumps(dict({"config": f"SEND kernels of one 256-tensor iteration ({a.tag})"}, **count_trace(a.count_trace))),
@@ -171,14 +187,14 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("send_bench: no HIP device")
     if a.trace:
-        trace(torch, a.trace)
+        trace(torch, a.trace, a.codec)
         return
     from stellatrain_amd.shard import c4_sizes
     only = set(a.only.split(","))
     for s in a.sets.split(","):
         label, sizes, nsets = {"c4": ("first 256 sizes of the C4 list", c4_sizes()[:256], 2),
                                "small": ("256 tensors of 60,000 floats", [60000] * 256, 4)}[s]
-        row = measure(torch, label, sizes, nsets, only, a.warmup, max(20, a.iters))
+        row = measure(torch, label, sizes, nsets, only, a.warmup, max(20, a.iters), a.codec)
         if a.tag:
             row["tree"] = a.tag
         print(json.dumps(row), flush=True)
