@@ -194,7 +194,9 @@ typedef struct stg_send_task {
  * and writes the wire form.  A single task of 2^22..2^24 elements keeps the
  * one-bucket scan with the sources summed inside its streaming pass.  Staging
  * takes 8 bytes per idx_cap slot of the call, kept with the workspace.
- *   thresholdv16 and threshold-v (STG_ERR_UNSUPPORTED for top-k).
+ *   thresholdv16, threshold-v and exact top-k.  STG_ERR_UNSUPPORTED for the
+ * shipped "topk": it writes idx[i] = i, so its selected entries have no true
+ * indices to zero.
  *   A threshold-v handle ("thresholdv"): the key is the pointer bucket.d_src
  * (thresholdv.cpp:44; `key` and idx_offset are ignored, and a key occurs twice
  * when two tasks with n > 0 share that pointer).  Its count varies, *d_count =
@@ -211,6 +213,23 @@ typedef struct stg_send_task {
  * also closes before min(2048, CUs) of them, a larger task runs alone through
  * the per-tensor scan and a copy to the residual), the residual copy fused;
  * then one finishing launch per 16 tasks (stg_debug_tv_batch_plan).
+ *   An exact top-k handle ("topk_exact"): the key is `key`, as for
+ * thresholdv16, and *d_count = idx_cap (topk.cpp:25; idx_cap < k is "Invalid
+ * parameter k").  The winners are the min(k, n) largest |x|, ties at the k-th
+ * magnitude taken in index order, emitted in index order with index +
+ * idx_offset; slots [min(k, n), W), W = min(idx_cap, n), are the wire form of
+ * (0, 0.0f), the block / tail split at 8 * ((W - 1) / 8), nothing past W
+ * written; under error feedback grad and residual are zeroed at the true index
+ * of every staged slot -- element 0 whenever min(k, n) < idx_cap -- and the
+ * residual ends equal to grad[0].  That is step 1 above into zeroed temporaries
+ * and step 2 with count = W.  The key's state ends as the per-tensor call
+ * leaves it for this purpose (threshold = this call's k-th magnitude), so
+ * batched and per-tensor calls on one key interleave freely; results never
+ * depend on it.  Launches: the gather launches as above; then five select
+ * launches per group of up to 16 tasks (topk_batch.hip: a task takes max(1,
+ * ceil(n / 8192)) tiles, a group also closes before one tile per CU, a larger
+ * task runs alone through the per-tensor top-k and a copy to the residual);
+ * then one finishing launch per 16 tasks (stg_debug_topk_batch_plan).
  *   All or nothing: every task is checked before any device call or key-state
  * change, and stg_last_error() names the offending task index.
  * STG_ERR_INVALID: a null handle, a null `tasks` with ntasks > 0, the
@@ -638,6 +657,17 @@ int stg_debug_publish_launches(const uint32_t *idx_caps, size_t ntasks, int num_
 int stg_debug_tv_batch_plan(const uint64_t *n, size_t ntasks, int num_cu, uint32_t *first_range,
                             uint32_t *launch_of);
 
+/* Diagnostics, plain host arithmetic (no device): the select groups an exact
+ * top-k stg_merge_send_batch_device call makes for tasks of n[i] floats on a
+ * device of num_cu compute units -- the rule the entry point packs by.
+ * launch[i]: the group of task i (0xffffffff for n[i] == 0: none);
+ * first_tile[i]: its first tile (workgroup) there (0 for a task that runs
+ * alone); *tile_cap: the tiles a group holds at most.  Returns the number of
+ * groups, a task with more tiles than the cap counting as its own, or -1 for a
+ * null array or num_cu <= 0. */
+int stg_debug_topk_batch_plan(const uint64_t *n, size_t ntasks, int num_cu, uint32_t *first_tile, uint32_t *launch,
+                              uint32_t *tile_cap);
+
 /* Gather-add from bf16 / fp16 gradient sources.  The node's other GPUs may
  * hold 16-bit model replicas (stg_param_publish_batch_device keeps them
  * current) and so produce 16-bit gradients; these entry points read them as
@@ -668,7 +698,8 @@ typedef struct stg_grad_src {
  *   stg_merge_send_batch_typed_device: srcs[i] is null -- task i then uses its
  * fp32 d_grads exactly as stg_merge_send_batch_device -- or a host array of
  * tasks[i].num_gpus typed sources, and tasks[i].d_grads is ignored (with
- * num_gpus == 1 the array holds only term0).  thresholdv16 and threshold-v.
+ * num_gpus == 1 the array holds only term0).  thresholdv16, threshold-v and
+ * exact top-k.
  *   Routing: a call whose sources are all fp32 and in place runs the fp32
  * entry point's launches.  Otherwise 16-bit sources load 16 (or 8) bytes per
  * lane and fp32 streams 16, in lane groups of 8 (or 4) elements, wherever one

@@ -163,6 +163,8 @@ _SIGS = {
     "stg_debug_publish_launches": (C.c_int, [C.POINTER(C.c_uint32), C.c_size_t, C.c_int]),
     "stg_debug_tv_batch_plan": (C.c_int, [C.POINTER(C.c_uint64), C.c_size_t, C.c_int, C.POINTER(C.c_uint32),
                                           C.POINTER(C.c_uint32)]),
+    "stg_debug_topk_batch_plan": (C.c_int, [C.POINTER(C.c_uint64), C.c_size_t, C.c_int, C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "stg_synth_fill_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_int, C.c_uint32, C.c_void_p]),
     "stg_last_error": (C.c_char_p, []),
 }

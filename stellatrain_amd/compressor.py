@@ -308,7 +308,17 @@ class Compressor:
         pairs.  ``dst_idx`` is int16 under flag 1 (else int32), ``dst_val``
         int16-typed fp16 bits under flag 2 (else float32); ``dst_idx.numel()``
         is the pair capacity.  Keys must be distinct within a call.
-        thresholdv16 and threshold-v (top-k: ``CodecError``, unsupported).
+        thresholdv16, threshold-v and exact top-k (the shipped ``"topk"``:
+        ``CodecError``, unsupported -- it writes ``idx[i] = i``, so there are
+        no true indices to zero).
+        On a ``TopkCompressor(exact=True)`` the key is ``key``, the count is
+        ``dst_idx.numel()`` (topk.cpp:25; it must be at least ``k``), the
+        first ``min(k, n)`` wire slots are the winners in index order (ties at
+        the k-th magnitude taken in index order) and slots ``[min(k, n), W)``,
+        ``W = min(dst_idx.numel(), n)``, the wire form of ``(0, 0.0)``; with
+        ``residual`` element 0 is zeroed whenever ``min(k, n) <
+        dst_idx.numel()``.  Batched and per-tensor calls on one key may
+        interleave in any order.
         On a ``ThresholdvCompressor`` the key is the pointer of the bucket
         (``key`` is ignored) and the count varies, ``min(qualifiers,
         dst_idx.numel())``, while the engine sends all ``W =

@@ -109,6 +109,9 @@ struct Workspace {
     std::mutex wire_mu;
     stg::DevBuf<uint32_t> wst_pos;
     stg::DevBuf<float> wst_val;
+    // batched exact top-k (topk_batch.hip): a select block per task slot of a
+    // group, zero at allocation and after every complete group
+    stg::DevBuf<stg::TopkBatchSel> tkb_sel;
 
     ~Workspace() {
         (void)hipSetDevice(device);
@@ -563,6 +566,32 @@ int ef_after(stg_codec *h, const stg_bucket_t &b, float *resid, bool fused, hipS
     return STG_OK;
 }
 
+// One top-k bucket (n > 0) through the per-tensor launches; the caller holds ws->mu.
+int run_topk_one(stg_codec *h, Workspace *ws, const stg_bucket_t &b, const void *key_ptr, hipEvent_t *ev,
+                 hipStream_t s) {
+    int rc;
+    const size_t n = b.n;
+    const size_t ntiles = (n + stg::TV_TILE - 1) / stg::TV_TILE;
+    // superset entries (two words each, stg::TOPK_SUP_CAP per tile); per-tile
+    // counts, their prefixes and the superset counts
+    // + the level-2 bin's list (two words per key)
+    // (whole groups of TK2_REG tiles: topk1.hip's fixed superset slots)
+    const size_t stiles = (ntiles + stg::TK2_REG - 1) / stg::TK2_REG * stg::TK2_REG;
+    if ((rc = ws->ensure(2 * stiles * stg::TOPK_SUP_CAP + 2 * stg::TOPK_LIST_CAP, 3 * ntiles + 1, 1))) return rc;
+    stg::TopkLaunch a{b.d_src, n, b.k, (uint32_t)b.idx_cap, b.d_idx, b.d_val, b.idx_offset, h->method == M_TOPK,
+                      b.d_count, h->num_cu, ev};
+    const size_t m = h->method == M_TOPK ? (n + 3) / 4 : n;
+    if ((m + stg::TV_TILE - 1) / stg::TV_TILE <= stg::TOPK_LIST_TILES) {
+        // one launch, steered by the key's last k-th magnitude (its first call: the select inside it)
+        KeyState *st;
+        bool fresh;
+        if ((rc = h->slot(state_key(h->method, b.key, key_ptr), &st, &fresh))) return rc;
+        HIP_TRY(stg::launch_topk1(a, ws->d, st, !fresh, &ws->tk_tag, s));
+    } else {
+        HIP_TRY(stg::launch_topk(a, ws->d, s));
+    }
+    return STG_OK;
+}
 
 int run_device(stg_codec *h, const char *key, const float *d_src, const void *key_ptr, size_t n, uint32_t k,
                uint32_t *d_idx, size_t idx_cap, float *d_val, size_t val_cap, int32_t idx_offset, uint32_t *d_count,
@@ -600,25 +629,8 @@ int run_device(stg_codec *h, const char *key, const float *d_src, const void *ke
         HIP_TRY(stg::launch_tv(a, ws->d, s));
         ws->tv_base += grid;
     } else {
-        const size_t ntiles = (n + stg::TV_TILE - 1) / stg::TV_TILE;
-        // superset entries (two words each, stg::TOPK_SUP_CAP per tile); per-tile
-        // counts, their prefixes and the superset counts
-        // + the level-2 bin's list (two words per key)
-        // (whole groups of TK2_REG tiles: topk1.hip's fixed superset slots)
-        const size_t stiles = (ntiles + stg::TK2_REG - 1) / stg::TK2_REG * stg::TK2_REG;
-        if ((rc = ws->ensure(2 * stiles * stg::TOPK_SUP_CAP + 2 * stg::TOPK_LIST_CAP, 3 * ntiles + 1, 1))) return rc;
-        stg::TopkLaunch a{d_src, n, k, (uint32_t)idx_cap, d_idx, d_val, idx_offset, h->method == M_TOPK, d_count,
-                          h->num_cu, ev};
-        const size_t m = h->method == M_TOPK ? (n + 3) / 4 : n;
-        if ((m + stg::TV_TILE - 1) / stg::TV_TILE <= stg::TOPK_LIST_TILES) {
-            // one launch, steered by the key's last k-th magnitude (its first call: the select inside it)
-            KeyState *st;
-            bool fresh;
-            if ((rc = h->slot(state_key(h->method, key, key_ptr), &st, &fresh))) return rc;
-            HIP_TRY(stg::launch_topk1(a, ws->d, st, !fresh, &ws->tk_tag, s));
-        } else {
-            HIP_TRY(stg::launch_topk(a, ws->d, s));
-        }
+        const stg_bucket_t b{key, d_src, n, k, d_idx, idx_cap, d_val, val_cap, idx_offset, d_count};
+        return run_topk_one(h, ws, b, key_ptr, ev, s);
     }
     return STG_OK;
 }
@@ -858,6 +870,97 @@ int run_tv_send(stg_codec *h, Workspace *ws, const stg_bucket_t *bk, float *cons
             // (tv_pass does not write the residual: the copy pass of the per-tensor sequence)
             if (res[i])
                 HIP_TRY(hipMemcpyAsync(res[i], b.d_src, b.n * sizeof(float), hipMemcpyDeviceToDevice, s));
+            return STG_OK;
+        });
+}
+
+// The select groups of an exact top-k send call (topk_batch.hip), by the one
+// rule the entry point and stg_debug_topk_batch_plan share: task i of n(i) > 0
+// floats takes topk_batch_tiles(n) tiles of a table that closes at SEND_BATCH
+// tasks or before topk_batch_tile_cap(num_cu) tiles; a task with more tiles
+// than the cap runs alone(i) -- the pending table is launched first, so the
+// groups keep the tasks' order.  fill(i, item) writes the item (blk0 and tiles
+// are set), launch(table, tiles) enqueues the group.
+template <class N, class Fill, class Launch, class Alone>
+int topk_batch_pack(size_t ntasks, int num_cu, N n, Fill fill, Launch launch, Alone alone) {
+    const uint64_t cap = stg::topk_batch_tile_cap(num_cu);
+    auto pk = stg::make_packer<stg::TopkBatch>(cap, launch);
+    for (size_t i = 0; i < ntasks; ++i) {
+        const uint64_t ni = n(i);
+        if (!ni) continue;
+        const uint64_t tiles = stg::topk_batch_tiles(ni);
+        if (tiles > cap) {
+            if (const int rc = pk.flush()) return rc;
+            if (const int rc = alone(i)) return rc;
+            continue;
+        }
+        stg::TopkBatchTask *d;
+        if (const int rc = pk.add(tiles, &d)) return rc;
+        d->tiles = (uint32_t)tiles;
+        fill(i, d);
+    }
+    return pk.flush();
+}
+
+// The exact top-k selects of a send call, after its gather launches: bk[i] is
+// task i's bucket with d_idx / d_val pointing into the staging, res[i] its
+// residual (the select's first pass copies the gathered bucket to it) or null.
+// Every task has passed validation: the key slots are taken here.
+int run_topk_send(stg_codec *h, Workspace *ws, const stg_bucket_t *bk, float *const *res, size_t ntasks,
+                  hipStream_t s) {
+    std::lock_guard<std::mutex> g(ws->mu);
+    int rc;
+    const uint64_t cap = stg::topk_batch_tile_cap(h->num_cu);
+    // the groups' per-tile counts (tile_cnt / tile_aux) and the per-slot select blocks, zero when fresh
+    if ((rc = ws->ensure(1, cap, 1))) return rc;
+    HIP_TRY(ws->tkb_sel.reserve(stg::SEND_BATCH, s, true));
+    std::vector<KeyState *> st(ntasks, nullptr);
+    for (size_t i = 0; i < ntasks; ++i) {
+        const stg_bucket_t &b = bk[i];
+        if (!b.n) {
+            HIP_TRY(hipMemsetAsync(b.d_count, 0, sizeof(uint32_t), s));
+            continue;
+        }
+        bool fresh;  // (a fresh slot is zero: the level-3 pick seeds it as tk2_seed does)
+        if (stg::topk_batch_tiles(b.n) <= cap &&
+            (rc = h->slot(state_key(h->method, b.key, b.d_src), &st[i], &fresh)))
+            return rc;
+    }
+    return topk_batch_pack(
+        ntasks, h->num_cu, [&](size_t i) { return (uint64_t)bk[i].n; },
+        [&](size_t i, stg::TopkBatchTask *d) {
+            const stg_bucket_t &b = bk[i];
+            d->src = b.d_src;
+            d->resid = res[i];
+            d->idx = b.d_idx;
+            d->val = b.d_val;
+            d->count_out = b.d_count;
+            d->state = st[i];
+            d->n = (uint32_t)b.n;
+            d->kk = (uint32_t)std::min<size_t>(b.k, b.n);
+            d->cap = (uint32_t)b.idx_cap;
+            d->slots = (uint32_t)std::min<size_t>(b.idx_cap, b.n);
+            d->idx_offset = b.idx_offset;
+        },
+        [&](stg::TopkBatch &w, uint32_t tiles) -> int {
+            for (uint32_t j = 0; j < w.nt; ++j) w.t[j].sel = ws->tkb_sel.get() + j;
+            w.tile_gt = ws->d.tile_cnt;
+            w.tile_eq = ws->d.tile_aux;
+            w.fail = ws->d.fail;
+            HIP_TRY(stg::launch_topk_batch(w, tiles, s));
+            return STG_OK;
+        },
+        [&](size_t i) -> int {
+            // the per-tensor route into the staging slice: slots [min(k, n), W) as the zeroed temporaries hold them
+            const stg_bucket_t &b = bk[i];
+            const size_t kk = std::min<size_t>(b.k, b.n), slots = std::min<size_t>(b.idx_cap, b.n);
+            if (slots > kk) {
+                HIP_TRY(hipMemsetAsync(b.d_idx + kk, 0, (slots - kk) * sizeof(uint32_t), s));
+                HIP_TRY(hipMemsetAsync(b.d_val + kk, 0, (slots - kk) * sizeof(float), s));
+            }
+            if ((rc = run_topk_one(h, ws, b, b.d_src, nullptr, s))) return rc;
+            // (the per-tensor launches do not write the residual: the copy pass of the per-tensor sequence)
+            if (res[i]) HIP_TRY(hipMemcpyAsync(res[i], b.d_src, b.n * sizeof(float), hipMemcpyDeviceToDevice, s));
             return STG_OK;
         });
 }
@@ -1102,9 +1205,10 @@ static int send_batch(stg_codec_t h, const stg_send_task_t *tasks, const stg_gra
     CritPath crit_path;
     if (!h) return fail(STG_ERR_INVALID, "null codec handle");
     if (ntasks && !tasks) return fail(STG_ERR_INVALID, "null task array");
-    if (h->method != M_TV16 && h->method != M_TV)
-        return fail(STG_ERR_UNSUPPORTED, "the one-call send path scans with thresholdv16 or thresholdv only "
-                                         "(gather-compress, then stg_wire_encode_device)");
+    if (h->method == M_TOPK)
+        return fail(STG_ERR_UNSUPPORTED, "the one-call send path takes thresholdv16, thresholdv or topk_exact: the "
+                                         "shipped top-k writes idx[i] = i, so its selected entries have no true "
+                                         "indices to zero (gather-compress, then stg_wire_encode_device)");
     // all or nothing: every task is checked before any device call or key state exists
     auto tfail = [](size_t i, int code, const std::string &msg) {
         return fail(code, "task " + std::to_string(i) + ": " + msg);
@@ -1182,12 +1286,13 @@ static int send_batch(stg_codec_t h, const stg_send_task_t *tasks, const stg_gra
     // own streaming pass (tv16lone.hip), one pass over the bucket instead of two.
     // That pass reads fp32 sources only: with a 16-bit source or a typed first
     // term the typed gather-add runs first, then the plain scan (the same bits).
-    // (thresholdv16's: a threshold-v task always takes the gather launches below)
-    const bool tv = h->method == M_TV;
-    const bool lone = !tv && live == 1 && tasks[one].bucket.n >= (size_t(1) << 22) &&
+    // (thresholdv16's: a threshold-v or top-k task always takes the gather launches below)
+    const bool tv = h->method == M_TV, topk = h->method == M_TOPK_EXACT;
+    const bool lone = !tv && !topk && live == 1 && tasks[one].bucket.n >= (size_t(1) << 22) &&
                       tasks[one].bucket.n <= (size_t(1) << 24);
-    // the scans of the call, after its gather launches
+    // the scans (top-k: the selects) of the call, after its gather launches
     auto scan = [&]() {
+        if (topk) return run_topk_send(h, ws, bk.data(), res.data(), ntasks, s);
         return tv ? run_tv_send(h, ws, bk.data(), res.data(), ntasks, s) : run_tv16(h, bk.data(), ntasks, s, res.data());
     };
     if (lone && any_typed) {
@@ -2488,6 +2593,32 @@ int stg_debug_tv_batch_plan(const uint64_t *n, size_t ntasks, int num_cu, uint32
             return STG_OK;
         });
     return launches;
+}
+
+int stg_debug_topk_batch_plan(const uint64_t *n, size_t ntasks, int num_cu, uint32_t *first_tile, uint32_t *launch,
+                              uint32_t *tile_cap) {
+    if (!n || !first_tile || !launch || !tile_cap || num_cu <= 0) return -1;
+    *tile_cap = (uint32_t)stg::topk_batch_tile_cap(num_cu);
+    int groups = 0;
+    for (size_t i = 0; i < ntasks; ++i) {
+        first_tile[i] = 0;
+        launch[i] = 0xffffffffu;  // (an empty task: no group)
+    }
+    topk_batch_pack(
+        ntasks, num_cu, [&](size_t i) { return n[i]; },
+        [&](size_t i, stg::TopkBatchTask *d) {
+            first_tile[i] = d->blk0;
+            launch[i] = (uint32_t)groups;
+        },
+        [&](stg::TopkBatch &, uint32_t) -> int {
+            ++groups;
+            return STG_OK;
+        },
+        [&](size_t i) -> int {
+            launch[i] = (uint32_t)groups++;
+            return STG_OK;
+        });
+    return groups;
 }
 
 int stg_synth_fill_device(float *d_dst, size_t n, uint64_t seed, int dist, uint32_t param, void *stream) {

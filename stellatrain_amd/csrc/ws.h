@@ -699,6 +699,56 @@ struct SendFinishDcBatch {
 };
 static_assert(sizeof(SendFinishDcBatch) <= 2048, "kernel arguments: stay well under 4 KiB");
 hipError_t launch_ef_pack_batch_dc(const SendFinishDcBatch &w, uint32_t blocks, hipStream_t s);
+// The same path for exact top-k (topk_batch.hip): a batched radix select and
+// ordered emission for up to SEND_BATCH tasks, then ef_pack_batch with count =
+// W = min(idx_cap, n) (the emission stages the unused slots as (0, 0.0f)).
+//
+// Tiles are TV_TILE floats, one 256-thread workgroup each: a task of n floats
+// takes topk_batch_tiles(n); a group closes at SEND_BATCH tasks or before its
+// tiles would pass topk_batch_tile_cap(num_cu); a task with more tiles than
+// that runs alone through launch_topk1 / launch_topk.
+inline uint64_t topk_batch_tiles(uint64_t n) { return std::max<uint64_t>(1, (n + TV_TILE - 1) / TV_TILE); }
+// One tile per compute unit: a group's five passes re-read at most num_cu x 32
+// KiB (8 MiB at 256 CUs), which stays in the cache between the launches, and
+// every pass is a single wave of workgroups.  Larger buckets are bandwidth
+// bound, where the per-tensor route reads the bucket once.
+inline uint64_t topk_batch_tile_cap(int num_cu) { return (uint64_t)std::max(num_cu, 1); }
+constexpr float TOPK_HINT_SEED = 1.0f / 256.0f;  // KeyState.inc of a key's first call (topk1.hip's D_SEED, tk2_seed)
+// A task slot's select block: zero at allocation and after every complete group
+// (the last workgroup of each pass zeroes what the pass filled).
+struct alignas(128) TopkBatchSel {
+    uint32_t done[3];              // workgroups done with level 1, 2, 3 (the last one picks, then zeroes it)
+    uint32_t prefix;               // bits of T fixed so far; T after level 3
+    uint32_t rank;                 // remaining descending rank inside the prefix
+    uint32_t cnt_gt;               // keys strictly above the prefix range; above T after level 3
+    uint32_t pad[26];
+    uint32_t hist[2048 + 2048 + 512];  // the three levels' bins (11 / 11 / 9 bits)
+};
+struct TopkBatchTask {
+    const float *src;              // the gathered grad[0]
+    float *resid;                  // receives every element of src (null: no error feedback)
+    uint32_t *idx;                 // staged pairs: indices (+ idx_offset) ...
+    float *val;                    // ... and values, slots of each written
+    uint32_t *count_out;           // = cap (POISON_COUNT after FAIL_SELECT)
+    KeyState *state;               // t = T, init = 1 (inc seeded when init was 0)
+    TopkBatchSel *sel;
+    uint32_t n;
+    uint32_t kk;                   // min(k, n) winners
+    uint32_t cap;                  // idx_cap
+    uint32_t slots;                // W = min(idx_cap, n): [kk, W) staged as (0, 0.0f)
+    int32_t idx_offset;
+    uint32_t blk0;                 // the task's first tile (workgroup) in the group
+    uint32_t tiles;                // topk_batch_tiles(n)
+};
+struct TopkBatch {
+    TopkBatchTask t[SEND_BATCH];
+    uint32_t nt;
+    uint32_t *tile_gt, *tile_eq;   // per tile of the group: keys > T and == T (ws.tile_cnt / ws.tile_aux)
+    uint32_t *fail;                // the workspace's sticky failure word
+};
+static_assert(sizeof(TopkBatch) <= 2048, "kernel arguments: stay well under 4 KiB");
+// tiles = the sum of the tasks' tiles <= topk_batch_tile_cap; five launches whatever nt is
+hipError_t launch_topk_batch(const TopkBatch &w, uint32_t tiles, hipStream_t s);
 // Publishing a step's changed parameters to the node's model replicas
 // (publish.hip): replica[j] = cvt(param[j]) at the indices of the step's
 // merged stream, for up to PUBLISH_BATCH tasks per launch.  The table --

@@ -147,7 +147,9 @@ class CodecEngine:
         as well: the key is then the bucket's pointer, the count varies, and
         all ``W = min(numel, n)`` slots are written -- the pairs, then the wire
         form of ``(0, 0.0)`` -- with element 0 zeroed by the error feedback
-        whenever the count is below ``W``
+        whenever the count is below ``W``; and under ``configure("topk_exact")``:
+        the ``numel`` largest magnitudes in index order, the count ``numel``
+        (``configure("topk")``, the shipped operator, is refused)
         (``Compressor.merge_send_batch_async``)."""
         import torch
         send, streams = [], []

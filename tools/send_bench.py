@@ -18,6 +18,8 @@ the median of --iters rounds after --warmup is reported, one JSON line per set.
   --only loop       runs on a tree without the batched call (the parent commit)
   --codec thresholdv  the same on a threshold-v handle (its loop zeroes the
                     temporaries first: the engine sends every slot)
+  --codec topk_exact  the same on an exact top-k handle (k <= n pairs are
+                    always written, so its loop needs no zeroing)
   --trace WAY       for a kernel trace run: warm up the 60,000-float set, then
                     one iteration of WAY between two stg_synth_fill_device
                     launches of 1 float (the only synth kernels of the run)
@@ -176,7 +178,7 @@ def main():
     p.add_argument("--trace", default=None)
     p.add_argument("--count-trace", default=None)
     p.add_argument("--tag", default="")
-    p.add_argument("--codec", default="thresholdv16", choices=["thresholdv16", "thresholdv"])
+    p.add_argument("--codec", default="thresholdv16", choices=["thresholdv16", "thresholdv", "topk_exact"])
     a = p.parse_args()
     if a.count_trace:
         print(json.dumps(dict({"config": f"SEND kernels of one 256-tensor iteration ({a.tag})"}, **count_trace(a.count_trace))),
