@@ -502,6 +502,45 @@ int stg_merge_optimize_adam_wire_device(stg_adam_t o, const char *name, float *d
                                         uint8_t *d_mark, uint32_t *d_out_idx, float *d_out_val,
                                         uint32_t *d_out_count, void *stream);
 
+/* The same MERGE decompress without any array as long as the parameter: no
+ * d_dense / d_mark, and work and scratch that follow the pairs, not n.  The
+ * pairs are bucketed by tile of 4,096 indices and every occupied tile is
+ * merged in LDS.  Per index the result is bitwise that of
+ * stg_scatter_merge_wire_device: indices >= n dropped, within a rank the last
+ * position of an index wins, the winners summed in rank order from +0.0f and
+ * divided by (float)world, zero values and the (0, 0.0) filler slots counted.
+ * The output is the union in ascending index order at every world -- at world
+ * 1 the pairs stg_scatter_merge_wire_device gives, sorted by index instead of
+ * kept in stream order -- *d_out_count its size, nothing written past it
+ * (0xffffffff after a device failure, which stg_scatter_merge_check reports).
+ * The optimizer entries step every emitted pair inside the emission at every
+ * world (amsgrad: the merge, then the step over its output); parameters and
+ * state are bitwise those of the _wire entries.
+ * Scratch, in the (device, stream) scratch of stg_scatter_merge_device, sized
+ * to the call (stg_merge_sparse_scratch_bytes; kept until a larger call or
+ * stg_scatter_merge_release), with T = ceil(n / 4096) tiles, P = world *
+ * per_rank pairs and L = min(T, P):
+ *     4 * world * T   pair counters per (tile, rank), zero between calls
+ *   + 12 * L          the occupied tiles, their union counts
+ *   + 12 * P          a record {position, index in tile} and a value per pair
+ *   + 16              device counts
+ * bytes -- 16.3 MB for n = 16 Mi, world 8, per_rank = 167,772, where the dense
+ * path takes 13 n = 218 MB; 12.6 MB for n = 2^32 - 1, world 3, per_rank = 600.
+ * STG_ERR_INVALID as stg_scatter_merge_wire_device without its d_dense /
+ * d_mark conditions; STG_ERR_UNSUPPORTED for n or per_rank of 2^32 or more, or
+ * world * per_rank of 2^32 or more.  per_rank == 0: count 0, no stream read. */
+int stg_scatter_merge_sparse_device(const stg_rank_stream_t *ranks, size_t per_rank, int world, size_t n,
+                                    uint32_t *d_out_idx, float *d_out_val, uint32_t *d_out_count, void *stream);
+int stg_merge_optimize_sgd_sparse_device(stg_sgd_t o, const char *name, float *d_param, uint32_t param_len,
+                                         const stg_rank_stream_t *ranks, size_t per_rank, int world,
+                                         uint32_t *d_out_idx, float *d_out_val, uint32_t *d_out_count, void *stream);
+int stg_merge_optimize_adam_sparse_device(stg_adam_t o, const char *name, float *d_param, uint32_t param_len,
+                                          const stg_rank_stream_t *ranks, size_t per_rank, int world,
+                                          uint32_t *d_out_idx, float *d_out_val, uint32_t *d_out_count, void *stream);
+/* The scratch bytes above for one call's shape.  Plain host arithmetic: needs
+ * no device.  Refuses what the entries refuse for their sizes. */
+int stg_merge_sparse_scratch_bytes(size_t per_rank, int world, size_t n, size_t *out);
+
 /* One ModuleCpuOptimize task of a batched call: the arguments of one
  * stg_merge_optimize_{sgd,adam}_wire_device call (param_len is n; `ranks` is a
  * host array of `world` entries, flag 0 = decoded u32 / f32). */

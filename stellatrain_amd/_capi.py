@@ -156,6 +156,15 @@ _SIGS = {
     "stg_merge_optimize_adam_wire_device": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                                       C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "stg_scatter_merge_sparse_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "stg_merge_optimize_sgd_sparse_device": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                       C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]),
+    "stg_merge_optimize_adam_sparse_device": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                        C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p]),
+    "stg_merge_sparse_scratch_bytes": (C.c_int, [C.c_size_t, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)]),
     "stg_merge_optimize_sgd_batch_device": (C.c_int, [C.c_void_p, C.POINTER(StgMergeTask), C.c_size_t, C.c_void_p]),
     "stg_merge_optimize_adam_batch_device": (C.c_int, [C.c_void_p, C.POINTER(StgMergeTask), C.c_size_t, C.c_void_p]),
     "stg_merge_batch_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

@@ -29,6 +29,7 @@
 #include "../../include/stg/codec.h"
 #include "batch_pack.h"
 #include "devbuf.h"
+#include "merge_sparse.h"
 #include "scan_grid.h"
 #include "ws.h"
 
@@ -656,6 +657,13 @@ struct MergeScratch {
     // are `win`, its tile counts `tiles`
     stg::DevBuf<float> wdense;
     stg::DevBuf<uint8_t> wmark;
+    // the sparse path (merge_sparse.hip): per (tile, rank) counters, zero at
+    // creation and after every call; the non-empty tiles and their union
+    // counts; a record and a value per pair; the call's device counts
+    stg::DevBuf<uint32_t> sp_cnt, sp_ucnt;
+    stg::DevBuf<uint2> sp_list, sp_rec;
+    stg::DevBuf<float> sp_val;
+    stg::DevBuf<stg::SparseCtl> sp_ctl;
     // kernel launches the batched entries have enqueued on this stream (stg_merge_batch_launches)
     uint64_t launches = 0;
     ~MergeScratch() { (void)hipSetDevice(device); }  // (the members free on this device)
@@ -1582,6 +1590,7 @@ struct MergeCall {
     float *out_val;
     uint32_t *out_count;
     void *stream;
+    bool sparse = false;              // a sparse entry: no dense / mark, the tile-bucketed path
 };
 
 // decoded pairs back to back: the wire form with flag 0
@@ -1614,6 +1623,7 @@ static int merge_check(const MergeCall &c) {
                 return fail(STG_ERR_INVALID, "rank stream buffer misaligned for its element type");
         }
     }
+    if (c.sparse) return STG_OK;  // no caller scratch
     if (c.world > 1 && (!c.dense || !c.mark)) return fail(STG_ERR_INVALID, "dense/mark scratch required for world > 1");
     if (c.world > 1 && (reinterpret_cast<uintptr_t>(c.mark) & 15u)) return fail(STG_ERR_INVALID, "mark scratch must be 16-byte aligned");
     // the emission reads and zeroes a lane's 16 dense floats as four float4
@@ -1656,9 +1666,60 @@ static int merge_run(const MergeCall &c, const stg::SgdLaunch *sgd = nullptr, co
     return merge_run_locked(c, ms.get(), ncu, sgd, adam);
 }
 
+// What the sparse path can index: uint32 indices, positions and record slots.
+static int sparse_size_check(size_t per_rank, int world, size_t n) {
+    if (world < 1) return fail(STG_ERR_INVALID, "world must be >= 1");
+    if (n >= (size_t(1) << 32) || per_rank >= (size_t(1) << 32))
+        return fail(STG_ERR_UNSUPPORTED, "more than 2^32-1 elements (uint32 indices)");
+    if (per_rank > 0xffffffffull / (size_t)world)
+        return fail(STG_ERR_UNSUPPORTED, "world * per_rank of 2^32 or more (uint32 record slots)");
+    return STG_OK;
+}
+
+// A checked sparse call (c.sparse) on the current device's (device, stream)
+// scratch: size its buffers to the call exactly, launch.  `w` carries the
+// fused step's fields (opt >= 0), as the policies' common / fill leave them.
+static int sparse_run(const MergeCall &c, stg::SparseArgs w = {}, int opt = -1) {
+    int rc = sparse_size_check(c.per_rank, c.world, c.n);
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(c.stream);
+    if (!c.per_rank) {  // nothing reads a stream
+        HIP_TRY(hipMemsetAsync(c.out_count, 0, sizeof(uint32_t), s));
+        return STG_OK;
+    }
+    int dev, ncu;
+    if ((rc = device_cus(&ncu, &dev))) return rc;
+    const std::shared_ptr<MergeScratch> ms = merge_scratch(dev, s);
+    std::lock_guard<std::mutex> g(ms->mu);
+    const stg::SparseSizes z = stg::sparse_sizes(c.per_rank, c.world, c.n);
+    const size_t words = std::max<size_t>((size_t)c.world * z.tiles, 1);
+    HIP_TRY(ms->fail.reserve(2, s, true));
+    HIP_TRY(ms->sp_cnt.reserve(words, s, true, nullptr, words));  // zeroed here, by the emission afterwards
+    HIP_TRY(ms->sp_list.reserve(z.list, s, false, nullptr, z.list));
+    HIP_TRY(ms->sp_ucnt.reserve(z.list, s, false, nullptr, z.list));
+    HIP_TRY(ms->sp_rec.reserve(z.pairs, s, false, nullptr, z.pairs));
+    HIP_TRY(ms->sp_val.reserve(z.pairs, s, false, nullptr, z.pairs));
+    HIP_TRY(ms->sp_ctl.reserve(1, s, true));
+    w.sc = stg::SparseScratch{ms->sp_cnt.get(), ms->sp_list.get(), ms->sp_ucnt.get(), ms->sp_rec.get(),
+                              ms->sp_val.get(), ms->sp_ctl.get(), ms->fail.get()};
+    w.n = c.n;
+    w.world = (uint32_t)c.world;
+    w.per_rank = (uint32_t)c.per_rank;
+    w.ntiles = (uint32_t)z.tiles;
+    w.cap = (uint32_t)z.pairs;
+    w.lcap = (uint32_t)z.list;
+    w.fworld = (float)c.world;
+    w.t.out_idx = c.out_idx;
+    w.t.out_val = c.out_val;
+    w.t.out_count = c.out_count;
+    HIP_TRY(stg::launch_merge_sparse(c.rs.data(), w, opt, ncu, s));
+    return STG_OK;
+}
+
 static int scatter_merge(const MergeCall &c) {
     int rc = merge_check(c);
-    return rc ? rc : merge_run(c);
+    if (rc) return rc;
+    return c.sparse ? sparse_run(c) : merge_run(c);
 }
 
 // The fused world-1 step's own limits (per_rank > 0 here).
@@ -1895,15 +1956,24 @@ static int merge_optimize(typename P::Handle o, const char *name, float *d_param
     if (!o || !name) return fail(STG_ERR_INVALID, "null argument");
     int rc = merge_check(c);
     if (rc) return rc;
+    if (c.sparse && (rc = sparse_size_check(c.per_rank, c.world, c.n))) return rc;
     HIP_TRY(hipSetDevice(o->device));
     // world 1: the election, then the emission with every winner's step in the
     // same pass (each index is elected once, so the updates commute).  Otherwise
     // the merge (of several ranks) first, then the step over its output.
-    const bool fused = c.world == 1 && c.per_rank != 0 && P::fuses(o);
-    if ((rc = fused ? merge_fused_limits(c, param_len) : merge_run(c))) return rc;
+    // The sparse path fuses at every world: its emission holds each index once.
+    const bool fused = (c.sparse ? param_len != 0 : c.world == 1) && c.per_rank != 0 && P::fuses(o);
+    if ((rc = fused ? merge_fused_limits(c, param_len) : c.sparse ? sparse_run(c) : merge_run(c))) return rc;
     typename P::Launch a;
     if ((rc = prepare<P>(o, name, d_param, param_len, static_cast<hipStream_t>(c.stream), &a))) return rc;
-    return fused ? merge_run(c, P::sgd(&a), P::adam(&a)) : merge_step<P>(o, a, c);
+    if (!fused) return merge_step<P>(o, a, c);
+    if (!c.sparse) return merge_run(c, P::sgd(&a), P::adam(&a));
+    stg::SparseArgs w{};
+    P::common(a, w);
+    P::fill(a, w.t);
+    w.t.param = d_param;
+    w.t.n = param_len;
+    return sparse_run(c, w, P::opt(a));
 }
 
 // ---- the iteration's ModuleCpuOptimize tasks in one call ----
@@ -2102,6 +2172,20 @@ int stg_scatter_merge_wire_device(const stg_rank_stream_t *ranks, size_t per_ran
                                    d_out_val, d_out_count, stream});
 }
 
+int stg_scatter_merge_sparse_device(const stg_rank_stream_t *ranks, size_t per_rank, int world, size_t n,
+                                    uint32_t *d_out_idx, float *d_out_val, uint32_t *d_out_count, void *stream) {
+    return scatter_merge(MergeCall{wire_streams(ranks, world), true, per_rank, world, n, nullptr, nullptr, d_out_idx,
+                                   d_out_val, d_out_count, stream, true});
+}
+
+int stg_merge_sparse_scratch_bytes(size_t per_rank, int world, size_t n, size_t *out) {
+    if (!out) return fail(STG_ERR_INVALID, "null argument");
+    *out = 0;
+    if (const int rc = sparse_size_check(per_rank, world, n)) return rc;
+    *out = stg::sparse_sizes(per_rank, world, n).bytes(world);
+    return STG_OK;
+}
+
 int stg_scatter_merge_check(void *stream) {
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
@@ -2118,8 +2202,8 @@ int stg_scatter_merge_check(void *stream) {
     uint32_t f = 0;
     if (ms->fail.get()) HIP_TRY(hipMemcpy(&f, ms->fail.get(), sizeof f, hipMemcpyDeviceToHost));
     if (f) {
-        char b[96];
-        snprintf(b, sizeof b, "MERGE decompress device failure flags 0x%x (a look-back gave up)", f);
+        char b[128];
+        snprintf(b, sizeof b, "MERGE decompress device failure flags 0x%x (1: a look-back gave up; 16: sparse scratch)", f);
         return fail(STG_ERR_DEVICE, b);
     }
     return STG_OK;
@@ -2203,6 +2287,14 @@ int stg_merge_optimize_sgd_wire_device(stg_sgd_t o, const char *name, float *d_p
     return merge_optimize<SgdBatch>(o, name, d_param, param_len,
                                     MergeCall{wire_streams(ranks, world), true, per_rank, world, param_len, d_dense, d_mark,
                                         d_out_idx, d_out_val, d_out_count, stream});
+}
+
+int stg_merge_optimize_sgd_sparse_device(stg_sgd_t o, const char *name, float *d_param, uint32_t param_len,
+                                         const stg_rank_stream_t *ranks, size_t per_rank, int world,
+                                         uint32_t *d_out_idx, float *d_out_val, uint32_t *d_out_count, void *stream) {
+    return merge_optimize<SgdBatch>(o, name, d_param, param_len,
+                                    MergeCall{wire_streams(ranks, world), true, per_rank, world, param_len, nullptr,
+                                        nullptr, d_out_idx, d_out_val, d_out_count, stream, true});
 }
 
 int stg_sgd_get_momentum(stg_sgd_t o, const char *name, float *host_out, uint32_t len, void *stream) {
@@ -2324,6 +2416,14 @@ int stg_merge_optimize_adam_wire_device(stg_adam_t o, const char *name, float *d
     return merge_optimize<AdamBatch>(o, name, d_param, param_len,
                                      MergeCall{wire_streams(ranks, world), true, per_rank, world, param_len, d_dense, d_mark,
                                          d_out_idx, d_out_val, d_out_count, stream});
+}
+
+int stg_merge_optimize_adam_sparse_device(stg_adam_t o, const char *name, float *d_param, uint32_t param_len,
+                                          const stg_rank_stream_t *ranks, size_t per_rank, int world,
+                                          uint32_t *d_out_idx, float *d_out_val, uint32_t *d_out_count, void *stream) {
+    return merge_optimize<AdamBatch>(o, name, d_param, param_len,
+                                     MergeCall{wire_streams(ranks, world), true, per_rank, world, param_len, nullptr,
+                                         nullptr, d_out_idx, d_out_val, d_out_count, stream, true});
 }
 
 int stg_merge_optimize_sgd_batch_device(stg_sgd_t o, const stg_merge_task_t *tasks, size_t ntasks, void *stream) {

@@ -25,7 +25,8 @@ from ._capi import (STG_DT_BF16, STG_DT_F16, STG_DT_F32, CodecError, StgMergeTas
 from .compressor import Compressor, make_compressor, typed_sources
 
 __all__ = ["CodecEngine", "SparseSGD", "MergeTasks", "merge_numel", "api_numel", "scatter_merge", "scatter_merge_wire",
-           "wire_decode_batch", "owner_of", "merge_batch_launches", "PublishTasks", "publish_params"]
+           "wire_decode_batch", "owner_of", "merge_batch_launches", "PublishTasks", "publish_params",
+           "scatter_merge_sparse", "merge_sparse_scratch_bytes"]
 
 
 def merge_numel(n: int, ratio: float, world: int = 1) -> int:
@@ -428,6 +429,42 @@ def scatter_merge_wire(streams, per_rank: int, n: int, dense=None, mark=None, ou
     return out_idx, out_val, count
 
 
+def scatter_merge_sparse(streams, per_rank: int, n: int, out_idx=None, out_val=None, count=None):
+    """``scatter_merge_wire`` without ``dense`` / ``mark``: the pairs are
+    bucketed by tile of 4,096 indices and merged in LDS, so work and scratch
+    (``merge_sparse_scratch_bytes``) follow the pairs, not ``n``.  The union in
+    ascending index order at every world, values bitwise those of
+    ``scatter_merge_wire``."""
+    import torch
+    world = len(streams)
+    arr = _rank_streams(streams, per_rank)
+    dev = streams[0][0].device
+    _, _, out_idx, out_val, count = _merge_outputs(dev, 0, per_rank * world, 1, None, None, out_idx, out_val, count)
+    check(lib().stg_scatter_merge_sparse_device(arr, per_rank, world, n, C.c_void_p(out_idx.data_ptr()),
+                                                C.c_void_p(out_val.data_ptr()), C.c_void_p(count.data_ptr()),
+                                                C.c_void_p(torch.cuda.current_stream(dev.index).cuda_stream)))
+    return out_idx, out_val, count
+
+
+def merge_sparse_scratch_bytes(per_rank: int, world: int, n: int) -> int:
+    """Bytes of library scratch one ``scatter_merge_sparse`` /
+    ``merge_optimize_sparse`` call of this shape needs (host arithmetic)."""
+    out = C.c_size_t()
+    check(lib().stg_merge_sparse_scratch_bytes(per_rank, world, n, C.byref(out)))
+    return out.value
+
+
+def _merge_optimize_sparse(fn, h, param, name, streams, per_rank, out_idx, out_val, count):
+    import torch
+    dev, world = param.device, len(streams)
+    arr = _rank_streams(streams, per_rank)
+    _, _, out_idx, out_val, count = _merge_outputs(dev, 0, per_rank * world, 1, None, None, out_idx, out_val, count)
+    check(fn(h, name.encode(), C.c_void_p(param.data_ptr()), param.numel(), arr, per_rank, world,
+             C.c_void_p(out_idx.data_ptr()), C.c_void_p(out_val.data_ptr()), C.c_void_p(count.data_ptr()),
+             C.c_void_p(torch.cuda.current_stream(dev.index).cuda_stream)))
+    return out_idx, out_val, count
+
+
 def _merge_optimize(fn, h, param, name, src, per_rank, world, dense, mark, out_idx, out_val, count):
     """ModuleCpuOptimize::run through one C call (``fn``): the MERGE decompress
     of ``world`` rank streams into the merged stream (returned), then the
@@ -688,6 +725,14 @@ class SparseSGD:
                                (_rank_streams(streams, per_rank),), per_rank, len(streams), dense, mark, out_idx,
                                out_val, count)
 
+    def merge_optimize_sparse(self, param, name: str, streams, per_rank: int, out_idx=None, out_val=None,
+                              count=None):
+        """``merge_optimize_wire`` through ``scatter_merge_sparse``: no
+        ``dense`` / ``mark``, the step inside the emission at every world;
+        parameters and state bitwise those of ``merge_optimize_wire``."""
+        return _merge_optimize_sparse(lib().stg_merge_optimize_sgd_sparse_device, self._h, param, name, streams,
+                                      per_rank, out_idx, out_val, count)
+
     def merge_optimize_batch(self, items):
         """``merge_optimize_wire`` on every item in order, in one call: items
         are ``(param, name, streams, per_rank[, dense, mark, out_idx, out_val,
@@ -757,6 +802,14 @@ class SparseAdam:
         return _merge_optimize(lib().stg_merge_optimize_adam_wire_device, self._h, param, name,
                                (_rank_streams(streams, per_rank),), per_rank, len(streams), dense, mark, out_idx,
                                out_val, count)
+
+    def merge_optimize_sparse(self, param, name: str, streams, per_rank: int, out_idx=None, out_val=None,
+                              count=None):
+        """``merge_optimize_wire`` through ``scatter_merge_sparse`` (see
+        ``SparseSGD.merge_optimize_sparse``); with amsgrad the merge, then the
+        step over its output."""
+        return _merge_optimize_sparse(lib().stg_merge_optimize_adam_sparse_device, self._h, param, name, streams,
+                                      per_rank, out_idx, out_val, count)
 
     def merge_optimize_batch(self, items):
         """``merge_optimize_wire`` on every item in order, in one call (see

@@ -20,6 +20,8 @@ times the other configs on one GPU and prints one JSON line per measurement:
   WMERGE  merge_optimize straight from wire-form rank streams against one
       wire_decode per rank plus the decoded call (60,000 floats and 64 MiB);
   BMERGE  merge_optimize_batch over 256 tensors against the per-tensor loop;
+  SMERGE  (--only smerge) the sparse MERGE decompress beside the dense path
+      (64 MiB at worlds 2 and 8, 60,000 floats at world 8);
   TVSEND  (--only tvsend) the one-call send path on a threshold-v handle over
       256 tensors against the per-tensor loop, three rotated cycles;
   E2E thresholdv16 64 MiB host-inclusive (serial and overlapped).
@@ -331,6 +333,35 @@ def merge_world(torch, calls, world=8):
     alg = world * 8.0 * k + 8.0 * int(oc.item()) + 5.0 * n  # pairs in, union out, dense + marks read once
     return {"config": f"MERGE decompress world={world}, 64 MiB bucket, k={k} per rank", "us_per_call": round(us, 2),
             "union": int(oc.item()), "alg_GBps": round(alg / us / 1e3, 1)}
+
+
+def sparse_merge(torch, calls):
+    """SMERGE: the tile-bucketed sparse MERGE decompress (scatter_merge_sparse)
+    beside the dense path (scatter_merge_wire) on the same decoded rank streams:
+    a 64 MiB bucket with k = 167,772 per rank at worlds 2 and 8, and 60,000
+    floats with k = 600 at world 8; streams as merge_world's.  A package
+    without the sparse entry gives the dense rows alone."""
+    import stellatrain_amd as S
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev)
+    for n, k, world in ((16 << 20, S.merge_numel(16 << 20, 0.99), 2), (16 << 20, S.merge_numel(16 << 20, 0.99), 8),
+                        (60000, 600, 8)):
+        g = torch.Generator(device="cpu").manual_seed(7)
+        streams = [(torch.sort(torch.randperm(n, generator=g)[:k]).values.to(torch.int32).to(dev),
+                    torch.randn(k, generator=g).to(dev), 0) for _ in range(world)]
+        dense = torch.zeros(n, dtype=torch.float32, device=dev)
+        mark = torch.zeros(n, dtype=torch.uint8, device=dev)
+        oi = torch.empty(world * k, dtype=torch.int32, device=dev)
+        ov = torch.empty(world * k, dtype=torch.float32, device=dev)
+        oc = torch.empty(1, dtype=torch.int32, device=dev)
+        paths = [("dense", lambda s: S.scatter_merge_wire(streams, k, n, dense, mark, oi, ov, oc))]
+        if hasattr(S, "scatter_merge_sparse"):
+            paths.append(("sparse", lambda s: S.scatter_merge_sparse(streams, k, n, oi, ov, oc)))
+        for path, fn in paths:
+            us = _time_loop(torch, st, fn, calls, 8)
+            alg = world * 8.0 * k + 8.0 * int(oc.item())  # pairs in, union out
+            yield {"config": f"SMERGE {path} world={world}, n={n}, k={k} per rank", "us_per_call": round(us, 2),
+                   "union": int(oc.item()), "pairs_GBps": round(alg / us / 1e3, 2)}
 
 
 def _time_loop(torch, st, fn, calls, warmup):
@@ -937,6 +968,9 @@ def main():
             emit(d)
     if "bmerge" in only:
         for d in batch_merge(torch):
+            emit(d)
+    if "smerge" in only:
+        for d in sparse_merge(torch, a.calls):
             emit(d)
 
 
