@@ -619,6 +619,50 @@ int stg_merge_optimize_adam_batch_device(stg_adam_t o, const stg_merge_task_t *t
  * STG_ERR_INVALID for a null `out`, before any device call. */
 int stg_merge_batch_launches(void *stream, uint64_t *out);
 
+/* The same tasks through the sparse path, in groups: the results -- parameters,
+ * momentum, last-touched words, m / v, every task's merged stream (ascending at
+ * every world) and count, the SGD iteration count, each name's Adam tick, the
+ * failure words -- are bitwise those of stg_merge_optimize_{sgd,adam}_sparse_device
+ * on tasks[0 .. ntasks-1] in order on `stream`; task i runs at iteration
+ * iter0 + i.  d_dense and d_mark are ignored: they may be null and are never
+ * read, written or checked.
+ *   A group is up to 16 consecutive tasks of one world (1 <= world <= 64),
+ * each with per_rank > 0 and a non-empty parameter, on an optimizer whose step
+ * fuses (SGD plain and smart, Adam without amsgrad).  It is one sparse call over
+ * the tensors laid side by side in a virtual tile space (tensor q owns tiles
+ * [tile0_q, tile0_q + ceil(n_q / 4096))) and takes 4 + 2 * ceil(world / 4)
+ * launches: 6 up to world 4, 8 at world 8.  It closes at 16 tasks, on a change
+ * of world, before a task whose name is already in it, before its tiles would
+ * pass STG_SPARSE_BATCH_TILES and before its pairs (world * the sum of
+ * per_rank) would pass STG_SPARSE_BATCH_PAIRS.  Its scratch, in the (device,
+ * stream) scratch, is stg_merge_sparse_scratch_bytes' formula with T and P the
+ * group's sums: at most 24 MiB of records and, at world 8, 2 MiB of counters.
+ * Tensors of different names must not overlap in memory.
+ *   A task that exceeds a cap by itself, a task with per_rank == 0, an empty
+ * parameter or world > 64, and every task of an amsgrad handle runs the
+ * per-tensor sparse sequence at its place in the order.
+ *   All or nothing, before any device call or state change, with the offending
+ * task index in stg_last_error(): a null handle, name or `tasks`, the conditions
+ * and sizes stg_merge_optimize_{sgd,adam}_sparse_device refuses, a param_len
+ * that differs from the name's first call or from an earlier task of the name.
+ * ntasks == 0 is STG_OK.  A disagreement inside a group's scratch poisons the
+ * counts of the group's tensors and sets the scratch's sticky failure word
+ * (stg_scatter_merge_check).  stg_merge_batch_launches counts these launches
+ * too. */
+#define STG_SPARSE_BATCH_TILES (1u << 16) /* tiles of 4,096 indices per group: its scans stay at 16 rounds */
+#define STG_SPARSE_BATCH_PAIRS (1u << 21) /* pairs per group: 24 MiB of records                              */
+int stg_merge_optimize_sgd_sparse_batch_device(stg_sgd_t o, const stg_merge_task_t *tasks, size_t ntasks,
+                                               void *stream);
+int stg_merge_optimize_adam_sparse_batch_device(stg_adam_t o, const stg_merge_task_t *tasks, size_t ntasks,
+                                                void *stream);
+/* The grouping above for tasks of the given shapes (n[i], per_rank[i],
+ * world[i]) with distinct names on an optimizer whose step fuses: group[i] is
+ * the index of task i's group within the call, or 0xffffffff where it runs the
+ * per-tensor sparse sequence.  Returns the number of groups; host arithmetic
+ * only.  STG_ERR_INVALID for a null array with ntasks > 0. */
+int stg_debug_merge_sparse_batch_plan(const uint64_t *n, const uint64_t *per_rank, const int *world, size_t ntasks,
+                                      uint32_t *group);
+
 /* Element types of a model replica (stg_replica_t.dtype). */
 #define STG_DT_F32  0
 #define STG_DT_BF16 1

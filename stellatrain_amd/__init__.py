@@ -11,6 +11,7 @@ from .compressor import (Compressor, SendTasks, ThresholdvCompressor, Thresholdv
                          TopkCompressor, make_compressor)
 from .engine import (CodecEngine, MergeTasks, PublishTasks, SparseAdam, SparseSGD, api_numel, merge_numel, owner_of,  # noqa: F401
                      gather_add, gather_slice, merge_batch_launches, publish_params, scatter_merge, scatter_merge_wire, wire_decode, wire_decode_batch,
-                     wire_encode, wire_encode_batch, wire_flag, merge_sparse_scratch_bytes, scatter_merge_sparse)
+                     wire_encode, wire_encode_batch, wire_flag, merge_sparse_batch_plan, merge_sparse_scratch_bytes,
+                     scatter_merge_sparse)
 
 __version__ = "0.1.0"

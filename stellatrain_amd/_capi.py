@@ -167,6 +167,12 @@ _SIGS = {
     "stg_merge_sparse_scratch_bytes": (C.c_int, [C.c_size_t, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)]),
     "stg_merge_optimize_sgd_batch_device": (C.c_int, [C.c_void_p, C.POINTER(StgMergeTask), C.c_size_t, C.c_void_p]),
     "stg_merge_optimize_adam_batch_device": (C.c_int, [C.c_void_p, C.POINTER(StgMergeTask), C.c_size_t, C.c_void_p]),
+    "stg_merge_optimize_sgd_sparse_batch_device": (C.c_int, [C.c_void_p, C.POINTER(StgMergeTask), C.c_size_t,
+                                                             C.c_void_p]),
+    "stg_merge_optimize_adam_sparse_batch_device": (C.c_int, [C.c_void_p, C.POINTER(StgMergeTask), C.c_size_t,
+                                                              C.c_void_p]),
+    "stg_debug_merge_sparse_batch_plan": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int),
+                                                    C.c_size_t, C.POINTER(C.c_uint32)]),
     "stg_merge_batch_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "stg_param_publish_batch_device": (C.c_int, [C.POINTER(StgPublishTask), C.c_size_t, C.c_void_p]),
     "stg_debug_publish_launches": (C.c_int, [C.POINTER(C.c_uint32), C.c_size_t, C.c_int]),

@@ -30,6 +30,7 @@
 #include "batch_pack.h"
 #include "devbuf.h"
 #include "merge_sparse.h"
+#include "merge_sparse_batch.h"
 #include "scan_grid.h"
 #include "ws.h"
 
@@ -1676,23 +1677,11 @@ static int sparse_size_check(size_t per_rank, int world, size_t n) {
     return STG_OK;
 }
 
-// A checked sparse call (c.sparse) on the current device's (device, stream)
-// scratch: size its buffers to the call exactly, launch.  `w` carries the
-// fused step's fields (opt >= 0), as the policies' common / fill leave them.
-static int sparse_run(const MergeCall &c, stg::SparseArgs w = {}, int opt = -1) {
-    int rc = sparse_size_check(c.per_rank, c.world, c.n);
-    if (rc) return rc;
-    hipStream_t s = static_cast<hipStream_t>(c.stream);
-    if (!c.per_rank) {  // nothing reads a stream
-        HIP_TRY(hipMemsetAsync(c.out_count, 0, sizeof(uint32_t), s));
-        return STG_OK;
-    }
-    int dev, ncu;
-    if ((rc = device_cus(&ncu, &dev))) return rc;
-    const std::shared_ptr<MergeScratch> ms = merge_scratch(dev, s);
-    std::lock_guard<std::mutex> g(ms->mu);
-    const stg::SparseSizes z = stg::sparse_sizes(c.per_rank, c.world, c.n);
-    const size_t words = std::max<size_t>((size_t)c.world * z.tiles, 1);
+// The sparse scratch sized to `z` exactly (caller holds ms->mu): the buffers
+// of one per-tensor call, or of one group of the batched entry.
+static int sparse_scratch_ensure(MergeScratch *ms, hipStream_t s, const stg::SparseSizes &z, int world,
+                                 stg::SparseScratch *out) {
+    const size_t words = std::max<size_t>((size_t)world * z.tiles, 1);
     HIP_TRY(ms->fail.reserve(2, s, true));
     HIP_TRY(ms->sp_cnt.reserve(words, s, true, nullptr, words));  // zeroed here, by the emission afterwards
     HIP_TRY(ms->sp_list.reserve(z.list, s, false, nullptr, z.list));
@@ -1700,8 +1689,21 @@ static int sparse_run(const MergeCall &c, stg::SparseArgs w = {}, int opt = -1) 
     HIP_TRY(ms->sp_rec.reserve(z.pairs, s, false, nullptr, z.pairs));
     HIP_TRY(ms->sp_val.reserve(z.pairs, s, false, nullptr, z.pairs));
     HIP_TRY(ms->sp_ctl.reserve(1, s, true));
-    w.sc = stg::SparseScratch{ms->sp_cnt.get(), ms->sp_list.get(), ms->sp_ucnt.get(), ms->sp_rec.get(),
+    *out = stg::SparseScratch{ms->sp_cnt.get(), ms->sp_list.get(), ms->sp_ucnt.get(), ms->sp_rec.get(),
                               ms->sp_val.get(), ms->sp_ctl.get(), ms->fail.get()};
+    return STG_OK;
+}
+
+// sparse_run on a scratch the caller has looked up and locked, as merge_run_locked.
+static int sparse_run_locked(const MergeCall &c, MergeScratch *ms, int ncu, stg::SparseArgs w = {}, int opt = -1,
+                             uint64_t *launches = nullptr) {
+    hipStream_t s = static_cast<hipStream_t>(c.stream);
+    if (!c.per_rank) {  // nothing reads a stream
+        HIP_TRY(hipMemsetAsync(c.out_count, 0, sizeof(uint32_t), s));
+        return STG_OK;
+    }
+    const stg::SparseSizes z = stg::sparse_sizes(c.per_rank, c.world, c.n);
+    if (const int rc = sparse_scratch_ensure(ms, s, z, c.world, &w.sc)) return rc;
     w.n = c.n;
     w.world = (uint32_t)c.world;
     w.per_rank = (uint32_t)c.per_rank;
@@ -1713,7 +1715,23 @@ static int sparse_run(const MergeCall &c, stg::SparseArgs w = {}, int opt = -1) 
     w.t.out_val = c.out_val;
     w.t.out_count = c.out_count;
     HIP_TRY(stg::launch_merge_sparse(c.rs.data(), w, opt, ncu, s));
+    // two bucketing passes of ceil(world / TB_RANKS) launches, the two scans, the two tile passes
+    stg::count_launch(launches, 4 + 2 * (uint32_t)((c.world + stg::TB_RANKS - 1) / stg::TB_RANKS));
     return STG_OK;
+}
+
+// A checked sparse call (c.sparse) on the current device's (device, stream)
+// scratch: size its buffers to the call exactly, launch.  `w` carries the
+// fused step's fields (opt >= 0), as the policies' common / fill leave them.
+static int sparse_run(const MergeCall &c, stg::SparseArgs w = {}, int opt = -1) {
+    int rc = sparse_size_check(c.per_rank, c.world, c.n);
+    if (rc) return rc;
+    if (!c.per_rank) return sparse_run_locked(c, nullptr, 0);  // (no scratch: nothing reads a stream)
+    int dev, ncu;
+    if ((rc = device_cus(&ncu, &dev))) return rc;
+    const std::shared_ptr<MergeScratch> ms = merge_scratch(dev, static_cast<hipStream_t>(c.stream));
+    std::lock_guard<std::mutex> g(ms->mu);
+    return sparse_run_locked(c, ms.get(), ncu, w, opt);
 }
 
 static int scatter_merge(const MergeCall &c) {
@@ -1977,6 +1995,38 @@ static int merge_optimize(typename P::Handle o, const char *name, float *d_param
 }
 
 // ---- the iteration's ModuleCpuOptimize tasks in one call ----
+// A refusal of task i: its index in front of the message.
+static int task_refuse(size_t i, int rc) {
+    g_err = "task " + std::to_string(i) + ": " + g_err;
+    return rc;
+}
+
+// The last checks of a batched call (a name's length against its first call
+// and against the call's earlier tasks), then the batch's iterations and
+// ticks, contiguous: task i prepares as the i-th call would.  One hold of the
+// handle's lock.
+template <class P>
+static int prepare_tasks(typename P::Handle o, const stg_merge_task_t *tasks, size_t ntasks, hipStream_t s,
+                         typename P::Launch *L) {
+    std::lock_guard<std::mutex> g(o->mu);
+    if (P::len_checked(o)) {
+        std::unordered_map<std::string, uint32_t> seen;
+        for (size_t i = 0; i < ntasks; ++i) {
+            int rc = P::len_check(o, tasks[i].name, tasks[i].param_len);
+            const auto ins = seen.emplace(tasks[i].name, tasks[i].param_len);
+            if (!rc && ins.first->second != tasks[i].param_len)
+                rc = fail(STG_ERR_INVALID, "param_len differs from an earlier task of the same name");
+            if (rc) return task_refuse(i, rc);
+        }
+    }
+    HIP_TRY(hipSetDevice(o->device));
+    for (size_t i = 0; i < ntasks; ++i) {
+        const int rc = P::prepare_locked(o, tasks[i].name, tasks[i].d_param, tasks[i].param_len, s, &L[i]);
+        if (rc) return task_refuse(i, rc);  // a HIP failure: the tasks before it keep their iterations
+    }
+    return STG_OK;
+}
+
 // elements (the sum of its tensors' n) a world > 1 group may hold: two winner
 // words each, so the winner words keep MERGE_BATCH_WIN_CAP
 constexpr size_t GROUP_CAP = stg::MERGE_BATCH_WIN_CAP / 2;
@@ -1985,10 +2035,7 @@ static int merge_optimize_batch(typename P::Handle o, const stg_merge_task_t *ta
     if (!o) return fail(STG_ERR_INVALID, "null argument");
     if (!ntasks) return STG_OK;
     if (!tasks) return fail(STG_ERR_INVALID, "null task array");
-    const auto refuse = [](size_t i, int rc) {
-        g_err = "task " + std::to_string(i) + ": " + g_err;
-        return rc;
-    };
+    const auto refuse = task_refuse;
     // every check of every task, before any device call or state change
     std::vector<MergeCall> calls;
     calls.reserve(ntasks);
@@ -2008,24 +2055,7 @@ static int merge_optimize_batch(typename P::Handle o, const stg_merge_task_t *ta
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     std::vector<typename P::Launch> L(ntasks);
-    {   // the batch's iterations and ticks, contiguous: task i prepares as the i-th call would
-        std::lock_guard<std::mutex> g(o->mu);
-        if (P::len_checked(o)) {
-            std::unordered_map<std::string, uint32_t> seen;
-            for (size_t i = 0; i < ntasks; ++i) {
-                int rc = P::len_check(o, tasks[i].name, tasks[i].param_len);
-                const auto ins = seen.emplace(tasks[i].name, tasks[i].param_len);
-                if (!rc && ins.first->second != tasks[i].param_len)
-                    rc = fail(STG_ERR_INVALID, "param_len differs from an earlier task of the same name");
-                if (rc) return refuse(i, rc);
-            }
-        }
-        HIP_TRY(hipSetDevice(o->device));
-        for (size_t i = 0; i < ntasks; ++i) {
-            const int rc = P::prepare_locked(o, tasks[i].name, tasks[i].d_param, tasks[i].param_len, s, &L[i]);
-            if (rc) return refuse(i, rc);  // a HIP failure: the tasks before it keep their iterations
-        }
-    }
+    if (const int rc = prepare_tasks<P>(o, tasks, ntasks, s, L.data())) return rc;
     int dev, ncu;
     if (const int rc = device_cus(&ncu, &dev)) return rc;
     const std::shared_ptr<MergeScratch> ms = merge_scratch(dev, s);
@@ -2152,6 +2182,129 @@ static int merge_optimize_batch(typename P::Handle o, const stg_merge_task_t *ta
     }
     if (const int rc = pk.flush()) return rc;
     return pw.flush();
+}
+
+// ---- the same tasks through the sparse path, in groups ----
+struct SparseShape {
+    uint64_t n, per_rank;
+    int world;
+};
+static_assert(stg::SB_TILE_CAP == STG_SPARSE_BATCH_TILES && stg::SB_PAIR_CAP == STG_SPARSE_BATCH_PAIRS,
+              "codec.h states the group's caps");
+// A task that can share a group's launches at all (else: the per-tensor sequence).
+static bool sparse_groupable(const SparseShape &z) {
+    return z.world >= 1 && (uint32_t)z.world <= stg::TB_RANKS && z.per_rank > 0 && z.n > 0 &&
+           (z.n + stg::TB_TILE - 1) / stg::TB_TILE <= stg::SB_TILE_CAP &&
+           z.per_rank <= stg::SB_PAIR_CAP / (uint64_t)z.world;
+}
+
+// The grouping the entry point and stg_debug_merge_sparse_batch_plan share:
+// consecutive groupable tasks of one world, up to MERGE_BATCH, closed before
+// the group's tiles would pass SB_TILE_CAP (the packer's limit), before its
+// pairs would pass SB_PAIR_CAP and before a task whose name is in it
+// (same(q, i)).  add(i, slot, table-or-null) fills task i's slot (the table
+// where it opens a group); launch(table, g0) runs the group that starts at
+// task g0 (nt, ntiles and cap set); lone(i) runs task i by itself.
+template <class Shape, class Same, class Add, class Launch, class Lone>
+static int sparse_batch_pack(size_t ntasks, bool fuses, Shape shape, Same same, Add add, Launch launch, Lone lone) {
+    size_t g0 = 0;
+    uint64_t pairs = 0;
+    auto pg = stg::make_packer<stg::SparseBatchArgs>(stg::SB_TILE_CAP, [&](stg::SparseBatchArgs &w, uint32_t tiles) -> int {
+        w.ntiles = tiles;
+        w.cap = (uint32_t)pairs;
+        pairs = 0;
+        return launch(w, g0);
+    });
+    for (size_t i = 0; i < ntasks; ++i) {
+        const SparseShape z = shape(i);
+        int rc;
+        if (!fuses || !sparse_groupable(z)) {  // at its place in the order
+            if ((rc = pg.flush()) || (rc = lone(i))) return rc;
+            continue;
+        }
+        const uint64_t p = (uint64_t)z.world * z.per_rank;
+        bool close = pg.count() && (shape(g0).world != z.world || pairs + p > stg::SB_PAIR_CAP);
+        for (size_t q = g0; !close && q < g0 + pg.count(); ++q) close = same(q, i);
+        if (close && (rc = pg.flush())) return rc;
+        stg::SparseBatchTensor *d;
+        if ((rc = pg.add((z.n + stg::TB_TILE - 1) / stg::TB_TILE, &d))) return rc;
+        if (pg.count() == 1) g0 = i;
+        d->n = (uint32_t)z.n;
+        d->ocap = (uint32_t)p;
+        pairs += p;
+        add(i, d, pg.count() == 1 ? &pg.table() : nullptr);
+    }
+    return pg.flush();
+}
+
+template <class P>
+static int merge_optimize_sparse_batch(typename P::Handle o, const stg_merge_task_t *tasks, size_t ntasks,
+                                       void *stream) {
+    if (!o) return fail(STG_ERR_INVALID, "null argument");
+    if (!ntasks) return STG_OK;
+    if (!tasks) return fail(STG_ERR_INVALID, "null task array");
+    // every check of every task, before any device call or state change
+    std::vector<MergeCall> calls;
+    calls.reserve(ntasks);
+    for (size_t i = 0; i < ntasks; ++i) {
+        const stg_merge_task_t &t = tasks[i];
+        if (!t.name) return task_refuse(i, fail(STG_ERR_INVALID, "null name"));
+        // (d_dense / d_mark: never looked at)
+        calls.push_back(MergeCall{wire_streams(t.ranks, t.world), true, t.per_rank, t.world, t.param_len, nullptr,
+                                  nullptr, t.d_out_idx, t.d_out_val, t.d_out_count, stream, true});
+        int rc = merge_check(calls[i]);
+        if (!rc) rc = sparse_size_check(t.per_rank, t.world, t.param_len);
+        if (rc) return task_refuse(i, rc);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::vector<typename P::Launch> L(ntasks);
+    if (const int rc = prepare_tasks<P>(o, tasks, ntasks, s, L.data())) return rc;
+    int dev, ncu;
+    if (const int rc = device_cus(&ncu, &dev)) return rc;
+    const std::shared_ptr<MergeScratch> ms = merge_scratch(dev, s);
+    std::lock_guard<std::mutex> g(ms->mu);
+    uint64_t *const launches = &ms->launches;
+    return sparse_batch_pack(
+        ntasks, P::fuses(o),
+        [&](size_t i) { return SparseShape{tasks[i].param_len, tasks[i].per_rank, tasks[i].world}; },
+        [&](size_t q, size_t i) { return strcmp(tasks[q].name, tasks[i].name) == 0; },
+        [&](size_t i, stg::SparseBatchTensor *d, stg::SparseBatchArgs *opened) {
+            if (opened) P::common(L[i], *opened);
+            d->out_idx = tasks[i].d_out_idx;
+            d->out_val = tasks[i].d_out_val;
+            d->out_count = tasks[i].d_out_count;
+            d->param = tasks[i].d_param;
+            P::fill(L[i], *d);
+        },
+        [&](stg::SparseBatchArgs &w, size_t g0) -> int {
+            // the scratch of one sparse call over the group's tile space: T and P are its sums
+            stg::SparseSizes z;
+            z.tiles = w.ntiles;
+            z.pairs = w.cap;
+            z.list = std::min(z.tiles, z.pairs);
+            const int world = tasks[g0].world;
+            if (const int rc = sparse_scratch_ensure(ms.get(), s, z, world, &w.sc)) return rc;
+            w.world = (uint32_t)world;
+            w.lcap = (uint32_t)z.list;
+            w.fworld = (float)world;
+            const stg::RankStream *ranks[stg::MERGE_BATCH];
+            for (uint32_t q = 0; q < w.nt; ++q) ranks[q] = calls[g0 + q].rs.data();
+            HIP_TRY(stg::launch_merge_sparse_batch(w, ranks, P::opt(L[g0]), ncu, s, launches));
+            return STG_OK;
+        },
+        [&](size_t i) -> int {  // the per-tensor sparse sequence, as merge_optimize runs it
+            const MergeCall &c = calls[i];
+            if (!(tasks[i].param_len != 0 && c.per_rank != 0 && P::fuses(o))) {
+                if (const int rc = sparse_run_locked(c, ms.get(), ncu, {}, -1, launches)) return rc;
+                return merge_step<P>(o, L[i], c, launches);
+            }
+            stg::SparseArgs w{};
+            P::common(L[i], w);
+            P::fill(L[i], w.t);
+            w.t.param = tasks[i].d_param;
+            w.t.n = tasks[i].param_len;
+            return sparse_run_locked(c, ms.get(), ncu, w, P::opt(L[i]), launches);
+        });
 }
 
 }  // namespace
@@ -2432,6 +2585,35 @@ int stg_merge_optimize_sgd_batch_device(stg_sgd_t o, const stg_merge_task_t *tas
 
 int stg_merge_optimize_adam_batch_device(stg_adam_t o, const stg_merge_task_t *tasks, size_t ntasks, void *stream) {
     return merge_optimize_batch<AdamBatch>(o, tasks, ntasks, stream);
+}
+
+int stg_merge_optimize_sgd_sparse_batch_device(stg_sgd_t o, const stg_merge_task_t *tasks, size_t ntasks,
+                                               void *stream) {
+    return merge_optimize_sparse_batch<SgdBatch>(o, tasks, ntasks, stream);
+}
+
+int stg_merge_optimize_adam_sparse_batch_device(stg_adam_t o, const stg_merge_task_t *tasks, size_t ntasks,
+                                                void *stream) {
+    return merge_optimize_sparse_batch<AdamBatch>(o, tasks, ntasks, stream);
+}
+
+int stg_debug_merge_sparse_batch_plan(const uint64_t *n, const uint64_t *per_rank, const int *world, size_t ntasks,
+                                      uint32_t *group) {
+    if (ntasks && (!n || !per_rank || !world || !group)) return STG_ERR_INVALID;
+    int groups = 0;
+    sparse_batch_pack(
+        ntasks, true, [&](size_t i) { return SparseShape{n[i], per_rank[i], world[i]}; },
+        [](size_t, size_t) { return false; },
+        [&](size_t i, stg::SparseBatchTensor *, stg::SparseBatchArgs *) { group[i] = (uint32_t)groups; },
+        [&](stg::SparseBatchArgs &, size_t) -> int {
+            ++groups;
+            return STG_OK;
+        },
+        [&](size_t i) -> int {
+            group[i] = 0xffffffffu;
+            return STG_OK;
+        });
+    return groups;
 }
 
 int stg_adam_get_state(stg_adam_t o, const char *name, float *host_m, float *host_v, uint32_t len,

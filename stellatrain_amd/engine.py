@@ -26,7 +26,7 @@ from .compressor import Compressor, make_compressor, typed_sources
 
 __all__ = ["CodecEngine", "SparseSGD", "MergeTasks", "merge_numel", "api_numel", "scatter_merge", "scatter_merge_wire",
            "wire_decode_batch", "owner_of", "merge_batch_launches", "PublishTasks", "publish_params",
-           "scatter_merge_sparse", "merge_sparse_scratch_bytes"]
+           "scatter_merge_sparse", "merge_sparse_scratch_bytes", "merge_sparse_batch_plan"]
 
 
 def merge_numel(n: int, ratio: float, world: int = 1) -> int:
@@ -446,6 +446,22 @@ def scatter_merge_sparse(streams, per_rank: int, n: int, out_idx=None, out_val=N
     return out_idx, out_val, count
 
 
+def merge_sparse_batch_plan(shapes) -> list:
+    """How ``merge_optimize_sparse_batch`` groups tasks of the given ``(n,
+    per_rank, world)`` shapes with distinct names on an optimizer whose step
+    fuses: per task the index of its group within the call, or None where it
+    runs ``merge_optimize_sparse`` by itself (host arithmetic)."""
+    shapes = list(shapes)
+    k = len(shapes)
+    n = (C.c_uint64 * max(k, 1))(*[z[0] for z in shapes])
+    m = (C.c_uint64 * max(k, 1))(*[z[1] for z in shapes])
+    w = (C.c_int * max(k, 1))(*[z[2] for z in shapes])
+    out = (C.c_uint32 * max(k, 1))()
+    if lib().stg_debug_merge_sparse_batch_plan(n, m, w, k, out) < 0:
+        raise ValueError("merge_sparse_batch_plan: bad arguments")
+    return [None if g == 0xffffffff else g for g in out[:k]]
+
+
 def merge_sparse_scratch_bytes(per_rank: int, world: int, n: int) -> int:
     """Bytes of library scratch one ``scatter_merge_sparse`` /
     ``merge_optimize_sparse`` call of this shape needs (host arithmetic)."""
@@ -496,11 +512,15 @@ class MergeTasks:
     same dense / mark scratch, left zero by each call; items that share a group
     work on the library's scratch instead), so read an iteration's merged
     streams before the next call.  The array keeps every tensor it
-    points at alive, the ones allocated here included."""
+    points at alive, the ones allocated here included.  ``sparse=True``: an
+    array for ``merge_optimize_sparse_batch``, which has no use for ``dense`` /
+    ``mark``: none is allocated, an item's own are dropped, and the tasks
+    carry null for both."""
 
-    def __init__(self, items):
+    def __init__(self, items, sparse: bool = False):
         import torch
         items = list(items)
+        self.sparse = bool(sparse)
         self.count = len(items)
         self.array = (StgMergeTask * max(self.count, 1))()
         self.outputs = []
@@ -523,12 +543,15 @@ class MergeTasks:
             if param.dtype != torch.float32 or not param.is_contiguous():
                 raise ValueError(f"merge_optimize_batch: item {j}: the parameter must be contiguous float32")
             world, n = len(streams), param.numel()
-            if world > 1:  # allocated here, not in _merge_outputs: it returns pointers only, and these must outlive it
+            if sparse:
+                dense = mark = None
+            elif world > 1:  # allocated here, not in _merge_outputs: it returns pointers only, and these must outlive it
                 if dense is None:
                     dense = torch.zeros(n, dtype=torch.float32, device=dev)
                 if mark is None:
                     mark = torch.zeros(n, dtype=torch.uint8, device=dev)
-            dp, mp, out_idx, out_val, count = _merge_outputs(dev, n, per_rank, world, dense, mark, out_idx, out_val,
+            dp, mp, out_idx, out_val, count = _merge_outputs(dev, n, per_rank * world if sparse else per_rank,
+                                                             1 if sparse else world, dense, mark, out_idx, out_val,
                                                              count)
             if out_idx.numel() < per_rank * world or out_val.numel() < per_rank * world:
                 raise ValueError(f"merge_optimize_batch: item {j}: output shorter than per_rank * world")
@@ -544,11 +567,11 @@ class MergeTasks:
         return [k[2] for k in self._keep]
 
 
-def _merge_optimize_batch(fn, h, items):
+def _merge_optimize_batch(fn, h, items, sparse: bool = False):
     """The iteration's ModuleCpuOptimize tasks through one C call (``fn``):
     ``items`` as ``MergeTasks`` takes them, or a prebuilt ``MergeTasks``."""
     import torch
-    tasks = items if isinstance(items, MergeTasks) else MergeTasks(items)
+    tasks = items if isinstance(items, MergeTasks) else MergeTasks(items, sparse=sparse)
     if not tasks.count:
         return []
     rc = fn(h, tasks.array, tasks.count, C.c_void_p(torch.cuda.current_stream(tasks.device.index).cuda_stream))
@@ -748,6 +771,19 @@ class SparseSGD:
         ``merge_batch_launches`` counts the launches."""
         return _merge_optimize_batch(lib().stg_merge_optimize_sgd_batch_device, self._h, items)
 
+    def merge_optimize_sparse_batch(self, items):
+        """``merge_optimize_sparse`` on every item in order, in one call:
+        bitwise the results of the loop, no ``dense`` / ``mark`` anywhere.
+        Consecutive items of one world (up to 16, distinct names, at most
+        65,536 tiles of 4,096 indices and 2 Mi pairs together) form a group
+        that shares 4 + 2 * ceil(world / 4) launches, on library scratch that
+        follows the group's pairs and tiles.  An item beyond a cap by itself,
+        an empty one and one of more than 64 ranks run ``merge_optimize_sparse``
+        at their place.  ``items`` as ``MergeTasks`` takes them (built with
+        ``sparse=True``), or a prebuilt ``MergeTasks``.  Returns a list of
+        (out_idx, out_val, count); ``merge_batch_launches`` counts the launches."""
+        return _merge_optimize_batch(lib().stg_merge_optimize_sgd_sparse_batch_device, self._h, items, sparse=True)
+
     def momentum_buffer(self, name: str, n: int):
         import torch
         out = np.zeros(n, np.float32)
@@ -816,6 +852,12 @@ class SparseAdam:
         ``SparseSGD.merge_optimize_batch``); with amsgrad every item runs one
         by one."""
         return _merge_optimize_batch(lib().stg_merge_optimize_adam_batch_device, self._h, items)
+
+    def merge_optimize_sparse_batch(self, items):
+        """``merge_optimize_sparse`` on every item in order, in one call (see
+        ``SparseSGD.merge_optimize_sparse_batch``); with amsgrad every item
+        runs one by one."""
+        return _merge_optimize_batch(lib().stg_merge_optimize_adam_sparse_batch_device, self._h, items, sparse=True)
 
     def check_device(self) -> None:
         """Raise if a device-side failure was flagged (amsgrad look-back timeout)."""

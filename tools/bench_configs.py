@@ -22,6 +22,8 @@ times the other configs on one GPU and prints one JSON line per measurement:
   BMERGE  merge_optimize_batch over 256 tensors against the per-tensor loop;
   SMERGE  (--only smerge) the sparse MERGE decompress beside the dense path
       (64 MiB at worlds 2 and 8, 60,000 floats at world 8);
+  BSMERGE (--only bsmerge) merge_optimize_sparse_batch over 256 tensors against
+      the per-tensor sparse loop and the dense merge_optimize_batch;
   TVSEND  (--only tvsend) the one-call send path on a threshold-v handle over
       256 tensors against the per-tensor loop, three rotated cycles;
   E2E thresholdv16 64 MiB host-inclusive (serial and overlapped).
@@ -838,6 +840,118 @@ def batch_merge(torch, repeats=7):
     return out
 
 
+def sparse_batch_merge(torch, repeats=7):
+    """An iteration's ModuleCpuOptimize tasks without dense scratch (SGD,
+    m = 0.9, world > 1): merge_optimize_sparse_batch against (1) the loop of
+    per-tensor merge_optimize_sparse calls, what a caller without dense scratch
+    has otherwise, and (2) the dense merge_optimize_batch -- same process, same
+    streams and output buffers, a handle each, alternating, `repeats` (>= 5)
+    synchronised sweeps each after two warm-up rounds, the median with min and
+    max; both batches marshalled on every call and from a prebuilt MergeTasks.
+    256 tensors of n = 60,000, k = 600 per rank at world 2 and 8 (u16 indices),
+    and the first 256 sizes of the C4 list at k = 1 %, world 2 (u32).  Rows
+    carry the launches of one call (merge_batch_launches; the loop's are 6 per
+    tensor up to 64 ranks) and each path's scratch bytes, computed from the
+    shapes: the largest per-tensor sparse scratch; for the dense batch the
+    caller's 5 n_max of dense / mark plus the library's 13 bytes per element of
+    its largest group (8 n_max where a tensor runs alone); the largest sparse
+    group's.  On a library without the sparse batch its columns are null."""
+    from stellatrain_amd import MergeTasks, SparseSGD, merge_batch_launches, merge_numel, merge_sparse_scratch_bytes, wire_encode
+    from stellatrain_amd.shard import c4_sizes
+    try:
+        from stellatrain_amd import merge_sparse_batch_plan
+    except ImportError:  # a library from before the sparse batch
+        merge_sparse_batch_plan = None
+    dev = torch.device("cuda", 0)
+    repeats = max(5, repeats)
+    out = []
+    gen = torch.Generator(device="cpu").manual_seed(29)
+    for label, sizes, world in (("256 tensors n=60000", [60000] * 256, 2), ("256 tensors n=60000", [60000] * 256, 8),
+                                ("first 256 sizes of the C4 list", c4_sizes()[:256], 2)):
+        flag = 1 if max(sizes) < 65536 else 0
+        dense = torch.zeros(max(sizes), dtype=torch.float32, device=dev)
+        mark = torch.zeros(max(sizes), dtype=torch.uint8, device=dev)
+        tasks = []
+        for j, n in enumerate(sizes):
+            k = merge_numel(n, 0.99)
+            stride = n // k
+            rs = []
+            for _ in range(world):
+                idx = (torch.arange(k, dtype=torch.int64) * stride + torch.randint(0, stride, (k,), generator=gen))
+                wi, wv = wire_encode(idx.to(torch.int32).to(dev), torch.randn(k, generator=gen).to(dev), flag)
+                rs.append((wi, wv, flag))
+            tasks.append((torch.zeros(n, dtype=torch.float32, device=dev), f"{j}@w", rs, k,
+                          torch.empty(k * world, dtype=torch.int32, device=dev),
+                          torch.empty(k * world, dtype=torch.float32, device=dev),
+                          torch.empty(1, dtype=torch.int32, device=dev)))
+        d_items = [(p, nm, rs, k, dense[:p.numel()], mark[:p.numel()], oi, ov, oc) for p, nm, rs, k, oi, ov, oc in tasks]
+        s_items = [(p, nm, rs, k, None, None, oi, ov, oc) for p, nm, rs, k, oi, ov, oc in tasks]
+        opts = {x: make_opt("sgd")[0] for x in ("sloop", "dense", "dense_pre", "sparse", "sparse_pre")}
+        has = hasattr(SparseSGD, "merge_optimize_sparse_batch")
+        d_pre = MergeTasks(d_items)
+        s_pre = MergeTasks(s_items, sparse=True) if has else None
+
+        def sloop():
+            for p, nm, rs, k, oi, ov, oc in tasks:
+                opts["sloop"].merge_optimize_sparse(p, nm, rs, k, oi, ov, oc)
+        fns = [("sloop", sloop), ("dense", lambda: opts["dense"].merge_optimize_batch(d_items)),
+               ("dense_pre", lambda: opts["dense_pre"].merge_optimize_batch(d_pre))]
+        if has:
+            fns += [("sparse", lambda: opts["sparse"].merge_optimize_sparse_batch(s_items)),
+                    ("sparse_pre", lambda: opts["sparse_pre"].merge_optimize_sparse_batch(s_pre))]
+        t = {name: [] for name, _ in fns}
+        launches = {}
+        for r in range(repeats + 2):  # two warm-up rounds (first calls create the state and size the scratch)
+            for name, fn in fns:
+                torch.cuda.synchronize()
+                before = merge_batch_launches()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                if r >= 2:
+                    t[name].append((time.perf_counter() - t0) * 1e6)
+                launches[name] = merge_batch_launches() - before
+        union = sum(int(x[6].item()) for x in tasks)
+        assert 0 < union <= sum(x[3] for x in tasks) * world
+        T = lambda n: (n + 4095) // 4096  # noqa: E731
+        sp_lone = [merge_sparse_scratch_bytes(x[3], world, n) for x, n in zip(tasks, sizes)]
+        groups, big, g, cnt = [0], [0], 0, 0  # the dense batch's groups: 16 tensors, 4 Mi elements
+        for n in sizes:
+            if n > 1 << 22:
+                big.append(n)
+                g = cnt = 0
+                continue
+            if cnt == 16 or g + n > 1 << 22:
+                g = cnt = 0
+            g, cnt = g + n, cnt + 1
+            groups.append(g)
+        sp_batch = None
+        if merge_sparse_batch_plan is not None:
+            plan = merge_sparse_batch_plan([(n, x[3], world) for x, n in zip(tasks, sizes)])
+            tp = {}
+            for gi, n, x in zip(plan, sizes, tasks):
+                if gi is not None:
+                    a = tp.setdefault(gi, [0, 0])
+                    a[0], a[1] = a[0] + T(n), a[1] + world * x[3]
+            sp_batch = max([4 * world * a + 12 * min(a, b) + 12 * b + 16 for a, b in tp.values()] +
+                           [z for z, gi in zip(sp_lone, plan) if gi is None])
+        row = {"config": f"BSMERGE merge_optimize SGD(m=0.9), {label}, k=1%, wire flag {flag}, world={world}",
+               "tensors": len(sizes), "floats": int(sum(sizes)), "union": union, "repeats": repeats,
+               "launches": {"sloop": 6 * len(sizes), **{k: v for k, v in launches.items() if k != "sloop"}},
+               "scratch_bytes": {"sloop": max(sp_lone), "dense": 5 * max(sizes) + max(13 * max(groups), 8 * max(big)),
+                                 "sparse": sp_batch}}
+        for name in ("sloop", "dense", "dense_pre", "sparse", "sparse_pre"):
+            v = t.get(name)
+            row[name + "_us"] = round(float(np.median(v)), 1) if v else None
+            row[name + "_us_min_max"] = [round(min(v), 1), round(max(v), 1)] if v else None
+        if has:
+            row["sloop_over_sparse_pre"] = round(row["sloop_us"] / row["sparse_pre_us"], 2)
+            row["dense_pre_over_sparse_pre"] = round(row["dense_pre_us"] / row["sparse_pre_us"], 2)
+        out.append(row)
+        del tasks, d_items, s_items, d_pre, s_pre, opts
+    return out
+
+
 def cpu_codec(method, mib, ratio, seconds):
     """The reference CPU path beside its GPU row, same run, this host's cores
     (north_star): oracle/_ref/libstg_ref.so (the reference's compress/*.cpp
@@ -971,6 +1085,9 @@ def main():
             emit(d)
     if "smerge" in only:
         for d in sparse_merge(torch, a.calls):
+            emit(d)
+    if "bsmerge" in only:
+        for d in sparse_batch_merge(torch):
             emit(d)
 
 
