@@ -668,6 +668,59 @@ int stg_debug_merge_sparse_batch_plan(const uint64_t *n, const uint64_t *per_ran
 #define STG_DT_BF16 1
 #define STG_DT_F16  2
 
+/* The MERGE decompress as the dense averaged gradient a dense optimizer reads:
+ * d_grad holds n elements of `dtype` (STG_DT_*), aligned to its element and no
+ * more.  merged[i] is the value stg_scatter_merge_sparse_device gives index i
+ * -- indices >= n dropped, within a rank the last position of an index wins,
+ * the winners summed in rank order from +0.0f and divided by (float)world,
+ * zero values and the (0, 0.0) filler slots counted -- and +0.0f where no rank
+ * wrote.  cvt is the identity for STG_DT_F32 and round-to-nearest-even for
+ * STG_DT_BF16 / STG_DT_F16 (overflow to inf, fp16 subnormals kept, a NaN stays
+ * a NaN).
+ *   accumulate == 0: d_grad[i] = cvt(merged[i]) for every i in [0, n), each
+ *     stored exactly once; nothing outside [0, n) is written.
+ *   accumulate != 0: d_grad[i] = cvt((float)d_grad[i] + merged[i]) at the
+ *     indices some rank wrote; every other element keeps its bits.
+ * per_rank >= 1 takes 2 + 2 * ceil(world / 64) launches: the sparse path's
+ * count, scan and placement, then one emission with a workgroup per tile of
+ * 4,096 indices.  A tile no pair fell into is told by one counter word: it
+ * stores zeros (accumulate: nothing) and reads no record.  per_rank == 0 reads
+ * no stream: one launch that stores zeros, or none under accumulate.  n == 0
+ * does nothing.  Scratch, failure word, check and release are those of
+ * stg_scatter_merge_sparse_device for the same shape (nothing as long as n);
+ * the pair counters are zero again when the call ends.
+ * STG_ERR_INVALID before any device call: world < 1, null `ranks` or a null
+ * buffer with per_rank > 0, a flag outside 0..3, a misaligned stream buffer, an
+ * unknown dtype, a null d_grad with n > 0, d_grad not aligned to its element.
+ * STG_ERR_UNSUPPORTED: the sizes stg_scatter_merge_sparse_device refuses. */
+int stg_merge_grad_device(const stg_rank_stream_t *ranks, size_t per_rank, int world, size_t n, void *d_grad,
+                          int dtype, int accumulate, void *stream);
+
+/* One tensor of a batched call: the arguments of one stg_merge_grad_device call. */
+typedef struct stg_grad_task {
+    const stg_rank_stream_t *ranks; /* `world` entries                              */
+    size_t per_rank;
+    int world;
+    size_t n;
+    void *d_grad;
+    int dtype;                      /* STG_DT_*                                     */
+    int accumulate;
+} stg_grad_task_t;                  /* 48 bytes on LP64: per_rank 8, world 16, n 24, d_grad 32, dtype 40 */
+
+/* tasks[0 .. ntasks-1] in order on `stream`, outputs bitwise those of
+ * stg_merge_grad_device on each.  Up to 16 consecutive tasks of one world
+ * (1 <= world <= 64), each with per_rank > 0 and n > 0, form a group as in
+ * stg_merge_optimize_*_sparse_batch_device (closed at 16 tasks, on a change of
+ * world, before STG_SPARSE_BATCH_TILES tiles or STG_SPARSE_BATCH_PAIRS pairs):
+ * its 1 + 2 * ceil(world / 4) bucketing launches and one emission over the
+ * group's tile space, types and modes mixed freely.  Any other task runs the
+ * per-tensor sequence at its place.  Outputs of one call must not overlap.
+ * All or nothing: every task is checked before any device call, with the task
+ * index in stg_last_error().  stg_merge_batch_launches counts these launches
+ * too.  ntasks == 0 is STG_OK; a null `tasks` with ntasks > 0 is
+ * STG_ERR_INVALID. */
+int stg_merge_grad_batch_device(const stg_grad_task_t *tasks, size_t ntasks, void *stream);
+
 /* One model copy that receives a task's changed parameters: param_len elements
  * of `dtype` at d_param, aligned to the element size (no more is needed). */
 typedef struct stg_replica {

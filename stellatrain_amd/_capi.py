@@ -76,6 +76,12 @@ class StgGradSrc(C.Structure):
     _fields_ = [("d_grad", C.c_void_p), ("dtype", C.c_int)]
 
 
+class StgGradTask(C.Structure):
+    """``stg_grad_task_t``: one tensor of ``stg_merge_grad_batch_device``."""
+    _fields_ = [("ranks", C.POINTER(StgRankStream)), ("per_rank", C.c_size_t), ("world", C.c_int), ("n", C.c_size_t),
+                ("d_grad", C.c_void_p), ("dtype", C.c_int), ("accumulate", C.c_int)]
+
+
 STG_DT_F32, STG_DT_BF16, STG_DT_F16 = 0, 1, 2
 
 _lib: C.CDLL | None = None
@@ -164,6 +170,9 @@ _SIGS = {
     "stg_merge_optimize_adam_sparse_device": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                                         C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                         C.c_void_p]),
+    "stg_merge_grad_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_void_p]),
+    "stg_merge_grad_batch_device": (C.c_int, [C.POINTER(StgGradTask), C.c_size_t, C.c_void_p]),
     "stg_merge_sparse_scratch_bytes": (C.c_int, [C.c_size_t, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)]),
     "stg_merge_optimize_sgd_batch_device": (C.c_int, [C.c_void_p, C.POINTER(StgMergeTask), C.c_size_t, C.c_void_p]),
     "stg_merge_optimize_adam_batch_device": (C.c_int, [C.c_void_p, C.POINTER(StgMergeTask), C.c_size_t, C.c_void_p]),

@@ -31,6 +31,7 @@
 #include "devbuf.h"
 #include "merge_sparse.h"
 #include "merge_sparse_batch.h"
+#include "merge_grad.h"
 #include "scan_grid.h"
 #include "ws.h"
 
@@ -2307,6 +2308,125 @@ static int merge_optimize_sparse_batch(typename P::Handle o, const stg_merge_tas
         });
 }
 
+// ---- the dense typed gradient (merge_grad.hip) ----
+static_assert(stg::GRAD_F32 == STG_DT_F32 && stg::GRAD_BF16 == STG_DT_BF16 && stg::GRAD_F16 == STG_DT_F16,
+              "codec.h states the element types");
+struct GradCall {
+    MergeCall c;       // a sparse wire call: streams, per_rank, world, n, stream
+    void *grad;
+    int dtype;
+    bool acc;
+};
+static GradCall grad_call(const stg_rank_stream_t *ranks, size_t per_rank, int world, size_t n, void *d_grad,
+                          int dtype, int accumulate, void *stream) {
+    return GradCall{MergeCall{wire_streams(ranks, world), true, per_rank, world, n, nullptr, nullptr, nullptr, nullptr,
+                              nullptr, stream, true},
+                    d_grad, dtype, accumulate != 0};
+}
+// Every refusal of the entries, none of which needs a device.
+static int grad_check(const GradCall &g) {
+    if (const int rc = merge_check(g.c)) return rc;
+    if (g.dtype != STG_DT_F32 && g.dtype != STG_DT_BF16 && g.dtype != STG_DT_F16)
+        return fail(STG_ERR_INVALID, "unknown gradient dtype");
+    if (g.c.n && !g.grad) return fail(STG_ERR_INVALID, "null gradient buffer");
+    if (reinterpret_cast<uintptr_t>(g.grad) & (g.dtype == STG_DT_F32 ? 3u : 1u))
+        return fail(STG_ERR_INVALID, "gradient buffer misaligned for its element type");
+    return sparse_size_check(g.c.per_rank, g.c.world, g.c.n);
+}
+// what a call enqueues nothing for
+static bool grad_idle(const GradCall &g) { return !g.c.n || (!g.c.per_rank && g.acc); }
+
+// One checked tensor on a scratch the caller has looked up and locked (null
+// for a call that buckets nothing: per_rank == 0).
+static int grad_run_locked(const GradCall &g, MergeScratch *ms, uint64_t *launches = nullptr) {
+    if (grad_idle(g)) return STG_OK;
+    const MergeCall &c = g.c;
+    hipStream_t s = static_cast<hipStream_t>(c.stream);
+    const stg::SparseSizes z = stg::sparse_sizes(c.per_rank, c.world, c.n);
+    stg::SparseArgs w{};
+    if (c.per_rank) {
+        if (const int rc = sparse_scratch_ensure(ms, s, z, c.world, &w.sc)) return rc;
+        w.n = c.n;
+        w.world = (uint32_t)c.world;
+        w.per_rank = (uint32_t)c.per_rank;
+        w.ntiles = (uint32_t)z.tiles;
+        w.cap = (uint32_t)z.pairs;
+        w.lcap = (uint32_t)z.list;
+        HIP_TRY(stg::launch_sparse_bucketing(c.rs.data(), w, s));
+        stg::count_launch(launches, 1 + 2 * (uint32_t)((c.world + stg::TB_RANKS - 1) / stg::TB_RANKS));
+    }
+    const stg::GradArgs a{w.sc,           g.grad,          c.n, (uint32_t)c.world, (uint32_t)z.tiles, (uint32_t)z.pairs,
+                          (uint32_t)z.list, (float)c.world};
+    HIP_TRY(stg::launch_grad_dense(a, g.dtype, g.acc, s));
+    stg::count_launch(launches);
+    return STG_OK;
+}
+
+static int grad_run(const GradCall &g) {
+    if (const int rc = grad_check(g)) return rc;
+    if (grad_idle(g)) return STG_OK;
+    if (!g.c.per_rank) return grad_run_locked(g, nullptr);  // (no scratch: nothing reads a stream)
+    int dev, ncu;
+    if (const int rc = device_cus(&ncu, &dev)) return rc;
+    const std::shared_ptr<MergeScratch> ms = merge_scratch(dev, static_cast<hipStream_t>(g.c.stream));
+    std::lock_guard<std::mutex> lk(ms->mu);
+    return grad_run_locked(g, ms.get());
+}
+
+static int grad_run_batch(const stg_grad_task_t *tasks, size_t ntasks, void *stream) {
+    if (!ntasks) return STG_OK;
+    if (!tasks) return fail(STG_ERR_INVALID, "null task array");
+    std::vector<GradCall> calls;
+    calls.reserve(ntasks);
+    bool idle = true;
+    for (size_t i = 0; i < ntasks; ++i) {  // every check of every task, before any device call
+        const stg_grad_task_t &t = tasks[i];
+        calls.push_back(grad_call(t.ranks, t.per_rank, t.world, t.n, t.d_grad, t.dtype, t.accumulate, stream));
+        if (const int rc = grad_check(calls[i])) return task_refuse(i, rc);
+        idle = idle && grad_idle(calls[i]);
+    }
+    if (idle) return STG_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int dev, ncu;
+    if (const int rc = device_cus(&ncu, &dev)) return rc;
+    const std::shared_ptr<MergeScratch> ms = merge_scratch(dev, s);
+    std::lock_guard<std::mutex> lk(ms->mu);
+    uint64_t *const launches = &ms->launches;
+    return sparse_batch_pack(
+        ntasks, true, [&](size_t i) { return SparseShape{tasks[i].n, tasks[i].per_rank, tasks[i].world}; },
+        [&](size_t, size_t) { return false; }, [&](size_t, stg::SparseBatchTensor *, stg::SparseBatchArgs *) {},
+        [&](stg::SparseBatchArgs &w, size_t g0) -> int {
+            // the scratch of one sparse call over the group's tile space, as the sparse batch sizes it
+            stg::SparseSizes z;
+            z.tiles = w.ntiles;
+            z.pairs = w.cap;
+            z.list = std::min(z.tiles, z.pairs);
+            const int world = tasks[g0].world;
+            if (const int rc = sparse_scratch_ensure(ms.get(), s, z, world, &w.sc)) return rc;
+            w.world = (uint32_t)world;
+            w.lcap = (uint32_t)z.list;
+            const stg::RankStream *ranks[stg::MERGE_BATCH];
+            stg::GradBatchArgs a{};
+            for (uint32_t q = 0; q < w.nt; ++q) {
+                const GradCall &g = calls[g0 + q];
+                ranks[q] = g.c.rs.data();
+                a.t[q] = stg::GradBatchTensor{g.grad, w.t[q].n, w.t[q].blk0, (uint32_t)g.dtype, g.acc ? 1u : 0u};
+            }
+            a.sc = w.sc;
+            a.nt = w.nt;
+            a.world = w.world;
+            a.ntiles = w.ntiles;
+            a.cap = w.cap;
+            a.lcap = w.lcap;
+            a.fworld = (float)world;
+            HIP_TRY(stg::launch_sparse_batch_bucketing(w, ranks, s, launches));
+            HIP_TRY(stg::launch_grad_dense_batch(a, s));
+            stg::count_launch(launches);
+            return STG_OK;
+        },
+        [&](size_t i) -> int { return grad_run_locked(calls[i], ms.get(), launches); });
+}
+
 }  // namespace
 
 extern "C" {
@@ -2329,6 +2449,15 @@ int stg_scatter_merge_sparse_device(const stg_rank_stream_t *ranks, size_t per_r
                                     uint32_t *d_out_idx, float *d_out_val, uint32_t *d_out_count, void *stream) {
     return scatter_merge(MergeCall{wire_streams(ranks, world), true, per_rank, world, n, nullptr, nullptr, d_out_idx,
                                    d_out_val, d_out_count, stream, true});
+}
+
+int stg_merge_grad_device(const stg_rank_stream_t *ranks, size_t per_rank, int world, size_t n, void *d_grad,
+                          int dtype, int accumulate, void *stream) {
+    return grad_run(grad_call(ranks, per_rank, world, n, d_grad, dtype, accumulate, stream));
+}
+
+int stg_merge_grad_batch_device(const stg_grad_task_t *tasks, size_t ntasks, void *stream) {
+    return grad_run_batch(tasks, ntasks, stream);
 }
 
 int stg_merge_sparse_scratch_bytes(size_t per_rank, int world, size_t n, size_t *out) {

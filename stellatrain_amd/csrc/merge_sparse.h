@@ -85,5 +85,8 @@ static_assert(sizeof(SparseRanks) + sizeof(SparseArgs) <= 3072, "kernel argument
 // union counts, their scan, emission.  opt: -1 = no step, else as
 // launch_merge_world_emit's.  `ranks` holds a.world host entries.
 hipError_t launch_merge_sparse(const RankStream *ranks, const SparseArgs &a, int opt, int num_cu, hipStream_t s);
+// Its first three (count, scan, place) alone, for an emission of another kind
+// (merge_grad.hip): reads a.sc, n, world, per_rank, ntiles, cap and lcap.
+hipError_t launch_sparse_bucketing(const RankStream *ranks, const SparseArgs &a, hipStream_t s);
 
 }  // namespace stg

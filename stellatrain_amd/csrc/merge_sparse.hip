@@ -307,7 +307,7 @@ hipError_t launch_emit(const SparseArgs &a, int opt, uint32_t grid, hipStream_t 
 
 }  // namespace
 
-hipError_t launch_merge_sparse(const RankStream *ranks, const SparseArgs &a, int opt, int num_cu, hipStream_t s) {
+hipError_t launch_sparse_bucketing(const RankStream *ranks, const SparseArgs &a, hipStream_t s) {
     BucketArgs b{a.sc, a.n, a.world, a.per_rank, (uint32_t)(((uint64_t)a.per_rank + TB_PAIRS - 1) / TB_PAIRS), a.cap};
     const auto bucket = [&](bool place) -> hipError_t {
         for (uint32_t r0 = 0; r0 < a.world; r0 += TB_RANKS) {
@@ -323,7 +323,11 @@ hipError_t launch_merge_sparse(const RankStream *ranks, const SparseArgs &a, int
     hipError_t e;
     if ((e = bucket(false)) != hipSuccess) return e;
     tb_scan<<<1, 1024, 0, s>>>(a);
-    if ((e = bucket(true)) != hipSuccess) return e;
+    return bucket(true);
+}
+
+hipError_t launch_merge_sparse(const RankStream *ranks, const SparseArgs &a, int opt, int num_cu, hipStream_t s) {
+    if (const hipError_t e = launch_sparse_bucketing(ranks, a, s); e != hipSuccess) return e;
     // four workgroups of 36 KiB per CU; never more than the list can hold
     const uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>(a.lcap, (uint32_t)std::max(num_cu, 1) * 4));
     tb_tile<0, -1><<<grid, STG_WG, 0, s>>>(a);

@@ -73,5 +73,10 @@ inline uint32_t sparse_batch_launches(uint32_t world) { return 4 + 2 * ((world +
 // ranks[q] holds tensor q's w.world host entries; opt as launch_merge_world_emit's.
 hipError_t launch_merge_sparse_batch(const SparseBatchArgs &w, const RankStream *const *ranks, int opt, int num_cu,
                                      hipStream_t s, uint64_t *launches = nullptr);
+// Its bucketing launches (count, scan, place) alone, for an emission of another
+// kind (merge_grad.hip): reads w.sc, nt, world, ntiles, cap, lcap and per tensor
+// n, blk0 and ocap.
+hipError_t launch_sparse_batch_bucketing(const SparseBatchArgs &w, const RankStream *const *ranks, hipStream_t s,
+                                         uint64_t *launches = nullptr);
 
 }  // namespace stg

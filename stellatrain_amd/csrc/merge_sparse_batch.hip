@@ -350,8 +350,8 @@ hipError_t launch_emit(const SparseBatchArgs &a, int opt, uint32_t grid, hipStre
 
 }  // namespace
 
-hipError_t launch_merge_sparse_batch(const SparseBatchArgs &w, const RankStream *const *ranks, int opt, int num_cu,
-                                     hipStream_t s, uint64_t *launches) {
+hipError_t launch_sparse_batch_bucketing(const SparseBatchArgs &w, const RankStream *const *ranks, hipStream_t s,
+                                         uint64_t *launches) {
     if (!w.nt || !w.world || w.world > TB_RANKS) return hipErrorInvalidValue;
     SparseBucketArgs b{};
     b.sc = w.sc;
@@ -387,7 +387,12 @@ hipError_t launch_merge_sparse_batch(const SparseBatchArgs &w, const RankStream 
     if ((e = bucket(false)) != hipSuccess) return e;
     sb_scan<<<1, 1024, 0, s>>>(w);
     count_launch(launches);
-    if ((e = bucket(true)) != hipSuccess) return e;
+    return bucket(true);
+}
+
+hipError_t launch_merge_sparse_batch(const SparseBatchArgs &w, const RankStream *const *ranks, int opt, int num_cu,
+                                     hipStream_t s, uint64_t *launches) {
+    if (const hipError_t e = launch_sparse_batch_bucketing(w, ranks, s, launches); e != hipSuccess) return e;
     // four workgroups of 36 KiB per CU; never more than the list can hold
     const uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>(w.lcap, (uint32_t)std::max(num_cu, 1) * 4));
     sb_tile<0, -1><<<grid, STG_WG, 0, s>>>(w);

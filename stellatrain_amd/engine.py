@@ -20,13 +20,14 @@ import ctypes as C
 
 import numpy as np
 
-from ._capi import (STG_DT_BF16, STG_DT_F16, STG_DT_F32, CodecError, StgMergeTask, StgPublishTask, StgRankStream,
+from ._capi import (STG_DT_BF16, STG_DT_F16, STG_DT_F32, CodecError, StgGradTask, StgMergeTask, StgPublishTask, StgRankStream,
                     StgReplica, StgWireRx, check, lib)
 from .compressor import Compressor, make_compressor, typed_sources
 
 __all__ = ["CodecEngine", "SparseSGD", "MergeTasks", "merge_numel", "api_numel", "scatter_merge", "scatter_merge_wire",
            "wire_decode_batch", "owner_of", "merge_batch_launches", "PublishTasks", "publish_params",
-           "scatter_merge_sparse", "merge_sparse_scratch_bytes", "merge_sparse_batch_plan"]
+           "scatter_merge_sparse", "merge_sparse_scratch_bytes", "merge_sparse_batch_plan", "merge_grad",
+           "merge_grad_batch", "GradTasks"]
 
 
 def merge_numel(n: int, ratio: float, world: int = 1) -> int:
@@ -444,6 +445,89 @@ def scatter_merge_sparse(streams, per_rank: int, n: int, out_idx=None, out_val=N
                                                 C.c_void_p(out_val.data_ptr()), C.c_void_p(count.data_ptr()),
                                                 C.c_void_p(torch.cuda.current_stream(dev.index).cuda_stream)))
     return out_idx, out_val, count
+
+
+def _grad_out(out, what: str) -> int:
+    """The ``STG_DT_*`` of a dense gradient output, after checking it."""
+    import torch
+    dts = {torch.float32: STG_DT_F32, torch.bfloat16: STG_DT_BF16, torch.float16: STG_DT_F16}
+    if out.dtype not in dts:
+        raise ValueError(f"{what}: dtype {out.dtype} is not float32, bfloat16 or float16")
+    if out.dim() != 1 or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous 1-D tensor")
+    return dts[out.dtype]
+
+
+def merge_grad(streams, per_rank: int, out, accumulate: bool = False):
+    """MERGE decompress into the dense averaged gradient: ``out`` (1-D float32,
+    bfloat16 or float16; ``n = out.numel()``) receives, at every index, what
+    ``scatter_merge_sparse`` gives it and +0.0 where no rank wrote, rounded to
+    nearest even for the 16-bit types.  ``accumulate=True`` adds to ``out`` at
+    the indices some rank wrote and leaves every other element alone (gradient
+    accumulation over micro-iterations).  ``streams`` as in
+    ``scatter_merge_wire``.  Four launches, no scratch as long as ``n``, no
+    host round trip.  Returns ``out``."""
+    import torch
+    dt = _grad_out(out, "merge_grad")
+    arr = _rank_streams(streams, per_rank)
+    dev = streams[0][0].device
+    if out.device != dev:
+        raise ValueError("merge_grad: out on a different device than the streams")
+    check(lib().stg_merge_grad_device(arr, per_rank, len(streams), out.numel(), C.c_void_p(out.data_ptr()), dt,
+                                      int(bool(accumulate)),
+                                      C.c_void_p(torch.cuda.current_stream(dev.index).cuda_stream)))
+    return out
+
+
+class GradTasks:
+    """A prebuilt ``stg_grad_task_t`` array for ``merge_grad_batch``,
+    marshalled and validated once (a model's gradient and receive buffers do
+    not move between iterations).  Each item is ``(streams, per_rank, out)`` or
+    ``(streams, per_rank, out, accumulate)``, as ``merge_grad`` takes them.
+    The array keeps every tensor it points at alive; ``outputs`` holds the
+    items' ``out`` tensors."""
+
+    def __init__(self, items):
+        items = list(items)
+        self.count = len(items)
+        self.array = (StgGradTask * max(self.count, 1))()
+        self.device = items[0][0][0][0].device if items and items[0][0] else None
+        self.outputs = []
+        self._keep = []
+        for j, it in enumerate(items):
+            if not 3 <= len(it) <= 4:
+                raise ValueError(f"merge_grad_batch: item {j}: (streams, per_rank, out[, accumulate]) expected")
+            streams, per_rank, out = it[:3]
+            acc = bool(it[3]) if len(it) == 4 else False
+            per_rank = int(per_rank)
+            try:
+                ranks = _rank_streams(streams, per_rank)
+                dt = _grad_out(out, "out")
+            except ValueError as e:
+                raise ValueError(f"merge_grad_batch: item {j}: {e}") from None
+            if streams[0][0].device != self.device or out.device != self.device:
+                raise ValueError(f"merge_grad_batch: item {j}: tensors on different devices")
+            self.array[j] = StgGradTask(ranks, per_rank, len(streams), out.numel(), out.data_ptr(), dt, int(acc))
+            self._keep.append((ranks, streams))
+            self.outputs.append(out)
+
+
+def merge_grad_batch(items):
+    """``merge_grad`` for many tensors through one C call: up to 16 consecutive
+    items of one world share their bucketing launches and one emission
+    (``stg_merge_grad_batch_device``); outputs are bitwise those of the loop.
+    ``items`` as ``GradTasks`` takes them, or a prebuilt ``GradTasks`` (no
+    per-call marshalling).  Returns the items' ``out`` tensors."""
+    import torch
+    tasks = items if isinstance(items, GradTasks) else GradTasks(items)
+    if not tasks.count:
+        return []
+    with torch.cuda.device(tasks.device):
+        rc = lib().stg_merge_grad_batch_device(
+            tasks.array, tasks.count, C.c_void_p(torch.cuda.current_stream(tasks.device.index).cuda_stream))
+    if rc:
+        check(rc)
+    return tasks.outputs
 
 
 def merge_sparse_batch_plan(shapes) -> list:

@@ -24,6 +24,9 @@ times the other configs on one GPU and prints one JSON line per measurement:
       (64 MiB at worlds 2 and 8, 60,000 floats at world 8);
   BSMERGE (--only bsmerge) merge_optimize_sparse_batch over 256 tensors against
       the per-tensor sparse loop and the dense merge_optimize_batch;
+  MGRAD   (--only merge_grad) merge_grad / merge_grad_batch (the dense typed
+      gradient) against today's sequence from public calls: scatter_merge_sparse,
+      the count read on the host, zero_(), index_put_ and a cast;
   TVSEND  (--only tvsend) the one-call send path on a threshold-v handle over
       256 tensors against the per-tensor loop, three rotated cycles;
   E2E thresholdv16 64 MiB host-inclusive (serial and overlapped).
@@ -364,6 +367,72 @@ def sparse_merge(torch, calls):
             alg = world * 8.0 * k + 8.0 * int(oc.item())  # pairs in, union out
             yield {"config": f"SMERGE {path} world={world}, n={n}, k={k} per rank", "us_per_call": round(us, 2),
                    "union": int(oc.item()), "pairs_GBps": round(alg / us / 1e3, 2)}
+
+
+def merge_grad_rows(torch, calls, repeats=5):
+    """MGRAD: the dense averaged gradient of a MERGE decompress, fp32 and bf16
+    outputs -- a 64 MiB bucket with k = 167,772 per rank at worlds 2 and 8, and
+    256 tensors of 60,000 floats with k = 600 at world 8 as a loop, one batched
+    call and a prebuilt batch.  "today" is what a user of the package without
+    merge_grad runs per tensor: scatter_merge_sparse, the count read on the
+    host, zero_(), index_put_ and (bf16) a cast.  Medians of `repeats` timed
+    loops between device events, the host's waits included."""
+    import statistics
+    import stellatrain_amd as S
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev)
+
+    def tensors(n, k, world, count, seed):
+        g = torch.Generator(device="cpu").manual_seed(seed)
+        return [[(torch.sort(torch.randperm(n, generator=g)[:k]).values.to(torch.int32).to(dev),
+                  torch.randn(k, generator=g).to(dev), 0) for _ in range(world)] for _ in range(count)]
+
+    def today(streams, k, n, oi, ov, oc, f32, out):
+        S.scatter_merge_sparse(streams, k, n, oi, ov, oc)
+        c = int(oc.item())
+        f32.zero_()
+        f32.index_put_((oi[:c].long(),), ov[:c])
+        if out is not f32:
+            out.copy_(f32)
+
+    def med(fn, ncalls):
+        return round(statistics.median(_time_loop(torch, st, fn, ncalls, 4 if r == 0 else 0) for r in range(repeats)), 2)
+
+    for dtype in (torch.float32, torch.bfloat16):
+        name = str(dtype).split(".")[1]
+        for world in (2, 8):
+            n, k = 16 << 20, S.merge_numel(16 << 20, 0.99)
+            streams = tensors(n, k, world, 1, 7)[0]
+            oi = torch.empty(world * k, dtype=torch.int32, device=dev)
+            ov = torch.empty(world * k, dtype=torch.float32, device=dev)
+            oc = torch.empty(1, dtype=torch.int32, device=dev)
+            f32 = torch.empty(n, dtype=torch.float32, device=dev)
+            out = f32 if dtype == torch.float32 else torch.empty(n, dtype=dtype, device=dev)
+            row = {"config": f"MGRAD {name} world={world}, n={n}, k={k} per rank"}
+            row["today_us"] = med(lambda s: today(streams, k, n, oi, ov, oc, f32, out), calls)
+            if hasattr(S, "merge_grad"):
+                row["merge_grad_us"] = med(lambda s: S.merge_grad(streams, k, out), calls)
+                row["accumulate_us"] = med(lambda s: S.merge_grad(streams, k, out, accumulate=True), calls)
+            yield row
+        n, k, world, count = 60000, 600, 8, 256
+        ts = tensors(n, k, world, count, 11)
+        oi = torch.empty(world * k, dtype=torch.int32, device=dev)
+        ov = torch.empty(world * k, dtype=torch.float32, device=dev)
+        oc = torch.empty(1, dtype=torch.int32, device=dev)
+        f32 = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(count)]
+        outs = f32 if dtype == torch.float32 else [torch.empty(n, dtype=dtype, device=dev) for _ in range(count)]
+        row = {"config": f"MGRAD {name} {count} x {n} floats, world={world}, k={k} per rank (us per {count} tensors)"}
+        row["today_us"] = med(lambda s: [today(t, k, n, oi, ov, oc, a, b) for t, a, b in zip(ts, f32, outs)], 3)
+        if hasattr(S, "merge_grad"):
+            items = [(t, k, o) for t, o in zip(ts, outs)]
+            pre = S.GradTasks(items)
+            row["loop_us"] = med(lambda s: [S.merge_grad(t, k, o) for t, k, o in items], 3)
+            row["batch_us"] = med(lambda s: S.merge_grad_batch(items), 3)
+            row["batch_prebuilt_us"] = med(lambda s: S.merge_grad_batch(pre), 3)
+            before = S.merge_batch_launches()
+            S.merge_grad_batch(pre)
+            row["batch_launches"] = S.merge_batch_launches() - before
+        yield row
 
 
 def _time_loop(torch, st, fn, calls, warmup):
@@ -1088,6 +1157,9 @@ def main():
             emit(d)
     if "bsmerge" in only:
         for d in sparse_batch_merge(torch):
+            emit(d)
+    if "merge_grad" in only:
+        for d in merge_grad_rows(torch, a.calls):
             emit(d)
 
 
