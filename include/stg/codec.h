@@ -721,6 +721,81 @@ typedef struct stg_grad_task {
  * STG_ERR_INVALID. */
 int stg_merge_grad_batch_device(const stg_grad_task_t *tasks, size_t ntasks, void *stream);
 
+/* The hyperparameters of one dense Adam / AdamW step, as torch.optim.Adam and
+ * AdamW name them (no amsgrad, no maximize).  `step` is the number of this
+ * step, 1 for the first.  decoupled != 0 is AdamW, 0 is Adam's L2 term. */
+typedef struct stg_adamw_hyper {
+    double lr, beta1, beta2, eps, weight_decay;
+    uint64_t step;
+    int decoupled;
+} stg_adamw_hyper_t;                /* 56 bytes on LP64: beta1 8, beta2 16, eps 24, weight_decay 32, step 40,
+                                       decoupled 48 */
+
+/* The MERGE decompress and the dense optimizer step that follows it, in the
+ * launches of stg_merge_grad_device: the dense gradient never exists in memory.
+ * With merged[i] as stg_merge_grad_device defines it (+0.0f where no rank
+ * wrote), for EVERY i in [0, n) -- torch's rule: moments decay and parameters
+ * move whether or not an index arrived -- in fp32, each operation rounded once,
+ * in this order:
+ *   x   = d_master ? d_master[i] : (float)d_param[i]
+ *   g   = merged[i]
+ *   decoupled:  x = x * (float)(1 - lr * weight_decay)
+ *   else:       g = g + (float)weight_decay * x
+ *   m'  = beta1 * m + (float)(1 - beta1) * g
+ *   v'  = beta2 * v + (float)(1 - beta2) * (g * g)
+ *   den = sqrtf(v') / (float)sqrt(1 - beta2^step) + eps
+ *   x'  = x - (float)(lr / (1 - beta1^step)) * (m' / den)
+ * (the constants computed in double and rounded once).  d_exp_avg[i] = m',
+ * d_exp_avg_sq[i] = v'; x' goes to d_master where there is one, and
+ * d_param[i] = cvt(x') with stg_merge_grad_device's cvt.  d_param holds n
+ * elements of `dtype`; d_master (null, or n floats beside a 16-bit d_param),
+ * d_exp_avg and d_exp_avg_sq hold n floats.  Each element of each array is
+ * loaded once and stored once; nothing outside [0, n) is touched.
+ * The entry keeps no state: the caller owns the moments and the master.
+ * Launches, scratch, failure word and check are those of stg_merge_grad_device
+ * without accumulate (per_rank == 0: one launch, every g is +0.0f; n == 0
+ * does nothing).
+ * STG_ERR_INVALID before any device call: whatever stg_merge_grad_device
+ * refuses (d_param standing for d_grad); a null hyper; with n > 0 a null
+ * d_exp_avg or d_exp_avg_sq; step == 0; a beta outside [0, 1); a negative or
+ * non-finite lr, eps or weight_decay; d_master beside STG_DT_F32; an fp32
+ * array not 4-byte aligned; fp32 arrays (the moments, and the fp32 parameter
+ * or the master) whose addresses are not congruent mod 16 -- slices of flat
+ * buffers at one element offset are.
+ * STG_ERR_UNSUPPORTED: the sizes stg_scatter_merge_sparse_device refuses. */
+int stg_merge_adamw_device(const stg_rank_stream_t *ranks, size_t per_rank, int world, size_t n, void *d_param,
+                           int dtype, float *d_master, float *d_exp_avg, float *d_exp_avg_sq,
+                           const stg_adamw_hyper_t *hyper, void *stream);
+
+/* One tensor of a batched call: pointers and sizes only, so a prebuilt array
+ * stays valid while lr and step change from one iteration to the next. */
+typedef struct stg_adamw_task {
+    const stg_rank_stream_t *ranks; /* `world` entries                              */
+    size_t per_rank;
+    int world;
+    size_t n;
+    void *d_param;
+    int dtype;                      /* STG_DT_*                                     */
+    float *d_master;                /* or NULL                                      */
+    float *d_exp_avg;
+    float *d_exp_avg_sq;
+} stg_adamw_task_t;                 /* 72 bytes on LP64: per_rank 8, world 16, n 24, d_param 32, dtype 40,
+                                       d_master 48, d_exp_avg 56, d_exp_avg_sq 64 */
+
+/* tasks[0 .. ntasks-1] in order on `stream`, every array bitwise what
+ * stg_merge_adamw_device leaves in it.  One hyper per call: a model with a
+ * decay and a no-decay parameter group makes two calls.  Grouping, caps and
+ * launches are those of stg_merge_grad_batch_device: a group of up to 16
+ * consecutive tasks of one world takes its 1 + 2 * ceil(world / 4) bucketing
+ * launches and one step launch over the group's tile space, types and masters
+ * mixed freely; any other task runs the per-tensor sequence at its place.
+ * Arrays of one call must not overlap.  All or nothing: every task is checked
+ * before any device call, with the task index in stg_last_error().
+ * stg_merge_batch_launches counts these launches too.  ntasks == 0 is STG_OK;
+ * a null `tasks` with ntasks > 0 is STG_ERR_INVALID. */
+int stg_merge_adamw_batch_device(const stg_adamw_task_t *tasks, size_t ntasks, const stg_adamw_hyper_t *hyper,
+                                 void *stream);
+
 /* One model copy that receives a task's changed parameters: param_len elements
  * of `dtype` at d_param, aligned to the element size (no more is needed). */
 typedef struct stg_replica {

@@ -82,6 +82,19 @@ class StgGradTask(C.Structure):
                 ("d_grad", C.c_void_p), ("dtype", C.c_int), ("accumulate", C.c_int)]
 
 
+class StgAdamwHyper(C.Structure):
+    """``stg_adamw_hyper_t``: the hyperparameters of one ``stg_merge_adamw*_device`` call."""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("weight_decay", C.c_double), ("step", C.c_uint64), ("decoupled", C.c_int)]
+
+
+class StgAdamwTask(C.Structure):
+    """``stg_adamw_task_t``: one tensor of ``stg_merge_adamw_batch_device``."""
+    _fields_ = [("ranks", C.POINTER(StgRankStream)), ("per_rank", C.c_size_t), ("world", C.c_int), ("n", C.c_size_t),
+                ("d_param", C.c_void_p), ("dtype", C.c_int), ("d_master", C.c_void_p), ("d_exp_avg", C.c_void_p),
+                ("d_exp_avg_sq", C.c_void_p)]
+
+
 STG_DT_F32, STG_DT_BF16, STG_DT_F16 = 0, 1, 2
 
 _lib: C.CDLL | None = None
@@ -173,6 +186,10 @@ _SIGS = {
     "stg_merge_grad_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_int,
                                         C.c_void_p]),
     "stg_merge_grad_batch_device": (C.c_int, [C.POINTER(StgGradTask), C.c_size_t, C.c_void_p]),
+    "stg_merge_adamw_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.POINTER(StgAdamwHyper), C.c_void_p]),
+    "stg_merge_adamw_batch_device": (C.c_int, [C.POINTER(StgAdamwTask), C.c_size_t, C.POINTER(StgAdamwHyper),
+                                               C.c_void_p]),
     "stg_merge_sparse_scratch_bytes": (C.c_int, [C.c_size_t, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)]),
     "stg_merge_optimize_sgd_batch_device": (C.c_int, [C.c_void_p, C.POINTER(StgMergeTask), C.c_size_t, C.c_void_p]),
     "stg_merge_optimize_adam_batch_device": (C.c_int, [C.c_void_p, C.POINTER(StgMergeTask), C.c_size_t, C.c_void_p]),

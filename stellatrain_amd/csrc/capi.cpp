@@ -32,6 +32,7 @@
 #include "merge_sparse.h"
 #include "merge_sparse_batch.h"
 #include "merge_grad.h"
+#include "merge_adamw.h"
 #include "scan_grid.h"
 #include "ws.h"
 
@@ -2427,6 +2428,161 @@ static int grad_run_batch(const stg_grad_task_t *tasks, size_t ntasks, void *str
         [&](size_t i) -> int { return grad_run_locked(calls[i], ms.get(), launches); });
 }
 
+// ---- the fused dense AdamW step (merge_adamw.hip) ----
+struct AdamwCall {
+    MergeCall c;       // a sparse wire call: streams, per_rank, world, n, stream
+    stg::AdamwTensor t;
+    int dtype;
+};
+static AdamwCall adamw_call(const stg_rank_stream_t *ranks, size_t per_rank, int world, size_t n, void *d_param,
+                            int dtype, float *d_master, float *d_m, float *d_v, void *stream) {
+    return AdamwCall{MergeCall{wire_streams(ranks, world), true, per_rank, world, n, nullptr, nullptr, nullptr,
+                               nullptr, nullptr, stream, true},
+                     stg::AdamwTensor{d_param, d_master, d_m, d_v}, dtype};
+}
+// The hyperparameters' refusals, and the constants the kernels read.
+static int adamw_hyper(const stg_adamw_hyper_t *y, stg::AdamwHyper *h) {
+    if (!y) return fail(STG_ERR_INVALID, "null hyper");
+    if (y->step == 0) return fail(STG_ERR_INVALID, "step must be >= 1 (the first step is 1)");
+    if (!(y->beta1 >= 0.0 && y->beta1 < 1.0) || !(y->beta2 >= 0.0 && y->beta2 < 1.0))
+        return fail(STG_ERR_INVALID, "beta outside [0, 1)");
+    if (!(y->lr >= 0.0) || !std::isfinite(y->lr)) return fail(STG_ERR_INVALID, "lr negative or not finite");
+    if (!(y->eps >= 0.0) || !std::isfinite(y->eps)) return fail(STG_ERR_INVALID, "eps negative or not finite");
+    if (!(y->weight_decay >= 0.0) || !std::isfinite(y->weight_decay))
+        return fail(STG_ERR_INVALID, "weight_decay negative or not finite");
+    const double step = (double)y->step;
+    h->decay = (float)(1.0 - y->lr * y->weight_decay);
+    h->wd = (float)y->weight_decay;
+    h->beta1 = (float)y->beta1;
+    h->omb1 = (float)(1.0 - y->beta1);
+    h->beta2 = (float)y->beta2;
+    h->omb2 = (float)(1.0 - y->beta2);
+    h->bc2s = (float)std::sqrt(1.0 - std::pow(y->beta2, step));
+    h->eps = (float)y->eps;
+    h->ss = (float)(y->lr / (1.0 - std::pow(y->beta1, step)));
+    h->decoupled = y->decoupled ? 1u : 0u;
+    return STG_OK;
+}
+// Every refusal of a tensor, none of which needs a device.
+static int adamw_check(const AdamwCall &a) {
+    if (const int rc = merge_check(a.c)) return rc;
+    if (a.dtype != STG_DT_F32 && a.dtype != STG_DT_BF16 && a.dtype != STG_DT_F16)
+        return fail(STG_ERR_INVALID, "unknown parameter dtype");
+    if (a.c.n && !a.t.param) return fail(STG_ERR_INVALID, "null parameter buffer");
+    if (reinterpret_cast<uintptr_t>(a.t.param) & (a.dtype == STG_DT_F32 ? 3u : 1u))
+        return fail(STG_ERR_INVALID, "parameter buffer misaligned for its element type");
+    if (a.c.n && (!a.t.m || !a.t.v)) return fail(STG_ERR_INVALID, "null exp_avg / exp_avg_sq buffer");
+    if (a.t.master && a.dtype == STG_DT_F32)
+        return fail(STG_ERR_INVALID, "a master beside an fp32 parameter (the parameter is the master)");
+    const void *f32[3] = {a.t.m, a.t.v, a.t.master ? a.t.master : a.dtype == STG_DT_F32 ? a.t.param : a.t.m};
+    for (const void *q : f32) {
+        if (!a.c.n) break;  // (nothing is dereferenced)
+        if (reinterpret_cast<uintptr_t>(q) & 3u) return fail(STG_ERR_INVALID, "fp32 array misaligned (4 bytes)");
+        if ((reinterpret_cast<uintptr_t>(q) ^ reinterpret_cast<uintptr_t>(f32[0])) & 15u)
+            return fail(STG_ERR_INVALID, "fp32 arrays not congruent mod 16 (one 16-byte phase for all)");
+    }
+    return sparse_size_check(a.c.per_rank, a.c.world, a.c.n);
+}
+
+// One checked tensor on a scratch the caller has looked up and locked (null
+// for a call that buckets nothing: per_rank == 0).
+static int adamw_run_locked(const AdamwCall &a, const stg::AdamwHyper &h, MergeScratch *ms,
+                            uint64_t *launches = nullptr) {
+    const MergeCall &c = a.c;
+    if (!c.n) return STG_OK;
+    hipStream_t s = static_cast<hipStream_t>(c.stream);
+    const stg::SparseSizes z = stg::sparse_sizes(c.per_rank, c.world, c.n);
+    stg::SparseArgs w{};
+    if (c.per_rank) {
+        if (const int rc = sparse_scratch_ensure(ms, s, z, c.world, &w.sc)) return rc;
+        w.n = c.n;
+        w.world = (uint32_t)c.world;
+        w.per_rank = (uint32_t)c.per_rank;
+        w.ntiles = (uint32_t)z.tiles;
+        w.cap = (uint32_t)z.pairs;
+        w.lcap = (uint32_t)z.list;
+        HIP_TRY(stg::launch_sparse_bucketing(c.rs.data(), w, s));
+        stg::count_launch(launches, 1 + 2 * (uint32_t)((c.world + stg::TB_RANKS - 1) / stg::TB_RANKS));
+    }
+    const stg::AdamwArgs k{w.sc, a.t, c.n, (uint32_t)c.world, (uint32_t)z.tiles, (uint32_t)z.pairs, (uint32_t)z.list,
+                           (float)c.world, h};
+    HIP_TRY(stg::launch_adamw_dense(k, a.dtype, s));
+    stg::count_launch(launches);
+    return STG_OK;
+}
+
+static int adamw_run(const AdamwCall &a, const stg_adamw_hyper_t *hyper) {
+    stg::AdamwHyper h;
+    if (const int rc = adamw_hyper(hyper, &h)) return rc;
+    if (const int rc = adamw_check(a)) return rc;
+    if (!a.c.n) return STG_OK;
+    if (!a.c.per_rank) return adamw_run_locked(a, h, nullptr);  // (no scratch: nothing reads a stream)
+    int dev, ncu;
+    if (const int rc = device_cus(&ncu, &dev)) return rc;
+    const std::shared_ptr<MergeScratch> ms = merge_scratch(dev, static_cast<hipStream_t>(a.c.stream));
+    std::lock_guard<std::mutex> lk(ms->mu);
+    return adamw_run_locked(a, h, ms.get());
+}
+
+static int adamw_run_batch(const stg_adamw_task_t *tasks, size_t ntasks, const stg_adamw_hyper_t *hyper,
+                           void *stream) {
+    if (!ntasks) return STG_OK;
+    if (!tasks) return fail(STG_ERR_INVALID, "null task array");
+    stg::AdamwHyper h;
+    if (const int rc = adamw_hyper(hyper, &h)) return rc;
+    std::vector<AdamwCall> calls;
+    calls.reserve(ntasks);
+    bool idle = true;
+    for (size_t i = 0; i < ntasks; ++i) {  // every check of every task, before any device call
+        const stg_adamw_task_t &t = tasks[i];
+        calls.push_back(adamw_call(t.ranks, t.per_rank, t.world, t.n, t.d_param, t.dtype, t.d_master, t.d_exp_avg,
+                                   t.d_exp_avg_sq, stream));
+        if (const int rc = adamw_check(calls[i])) return task_refuse(i, rc);
+        idle = idle && !t.n;
+    }
+    if (idle) return STG_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int dev, ncu;
+    if (const int rc = device_cus(&ncu, &dev)) return rc;
+    const std::shared_ptr<MergeScratch> ms = merge_scratch(dev, s);
+    std::lock_guard<std::mutex> lk(ms->mu);
+    uint64_t *const launches = &ms->launches;
+    return sparse_batch_pack(
+        ntasks, true, [&](size_t i) { return SparseShape{tasks[i].n, tasks[i].per_rank, tasks[i].world}; },
+        [&](size_t, size_t) { return false; }, [&](size_t, stg::SparseBatchTensor *, stg::SparseBatchArgs *) {},
+        [&](stg::SparseBatchArgs &w, size_t g0) -> int {
+            // the scratch of one sparse call over the group's tile space, as the sparse batch sizes it
+            stg::SparseSizes z;
+            z.tiles = w.ntiles;
+            z.pairs = w.cap;
+            z.list = std::min(z.tiles, z.pairs);
+            const int world = tasks[g0].world;
+            if (const int rc = sparse_scratch_ensure(ms.get(), s, z, world, &w.sc)) return rc;
+            w.world = (uint32_t)world;
+            w.lcap = (uint32_t)z.list;
+            const stg::RankStream *ranks[stg::MERGE_BATCH];
+            stg::AdamwBatchArgs a{};
+            for (uint32_t q = 0; q < w.nt; ++q) {
+                const AdamwCall &k = calls[g0 + q];
+                ranks[q] = k.c.rs.data();
+                a.t[q] = stg::AdamwBatchTensor{k.t, w.t[q].n, w.t[q].blk0, (uint32_t)k.dtype, 0u};
+            }
+            a.sc = w.sc;
+            a.nt = w.nt;
+            a.world = w.world;
+            a.ntiles = w.ntiles;
+            a.cap = w.cap;
+            a.lcap = w.lcap;
+            a.fworld = (float)world;
+            a.h = h;
+            HIP_TRY(stg::launch_sparse_batch_bucketing(w, ranks, s, launches));
+            HIP_TRY(stg::launch_adamw_dense_batch(a, s));
+            stg::count_launch(launches);
+            return STG_OK;
+        },
+        [&](size_t i) -> int { return adamw_run_locked(calls[i], h, ms.get(), launches); });
+}
+
 }  // namespace
 
 extern "C" {
@@ -2458,6 +2614,18 @@ int stg_merge_grad_device(const stg_rank_stream_t *ranks, size_t per_rank, int w
 
 int stg_merge_grad_batch_device(const stg_grad_task_t *tasks, size_t ntasks, void *stream) {
     return grad_run_batch(tasks, ntasks, stream);
+}
+
+int stg_merge_adamw_device(const stg_rank_stream_t *ranks, size_t per_rank, int world, size_t n, void *d_param,
+                           int dtype, float *d_master, float *d_exp_avg, float *d_exp_avg_sq,
+                           const stg_adamw_hyper_t *hyper, void *stream) {
+    return adamw_run(adamw_call(ranks, per_rank, world, n, d_param, dtype, d_master, d_exp_avg, d_exp_avg_sq, stream),
+                     hyper);
+}
+
+int stg_merge_adamw_batch_device(const stg_adamw_task_t *tasks, size_t ntasks, const stg_adamw_hyper_t *hyper,
+                                 void *stream) {
+    return adamw_run_batch(tasks, ntasks, hyper, stream);
 }
 
 int stg_merge_sparse_scratch_bytes(size_t per_rank, int world, size_t n, size_t *out) {

@@ -20,14 +20,14 @@ import ctypes as C
 
 import numpy as np
 
-from ._capi import (STG_DT_BF16, STG_DT_F16, STG_DT_F32, CodecError, StgGradTask, StgMergeTask, StgPublishTask, StgRankStream,
+from ._capi import (STG_DT_BF16, STG_DT_F16, STG_DT_F32, CodecError, StgAdamwHyper, StgAdamwTask, StgGradTask, StgMergeTask, StgPublishTask, StgRankStream,
                     StgReplica, StgWireRx, check, lib)
 from .compressor import Compressor, make_compressor, typed_sources
 
 __all__ = ["CodecEngine", "SparseSGD", "MergeTasks", "merge_numel", "api_numel", "scatter_merge", "scatter_merge_wire",
            "wire_decode_batch", "owner_of", "merge_batch_launches", "PublishTasks", "publish_params",
            "scatter_merge_sparse", "merge_sparse_scratch_bytes", "merge_sparse_batch_plan", "merge_grad",
-           "merge_grad_batch", "GradTasks"]
+           "merge_grad_batch", "GradTasks", "merge_adamw", "merge_adamw_batch", "AdamWTasks"]
 
 
 def merge_numel(n: int, ratio: float, world: int = 1) -> int:
@@ -525,6 +525,112 @@ def merge_grad_batch(items):
     with torch.cuda.device(tasks.device):
         rc = lib().stg_merge_grad_batch_device(
             tasks.array, tasks.count, C.c_void_p(torch.cuda.current_stream(tasks.device.index).cuda_stream))
+    if rc:
+        check(rc)
+    return tasks.outputs
+
+
+def _adamw_state(what: str, param, exp_avg, exp_avg_sq, master):
+    """(``STG_DT_*`` of ``param``, master pointer or None) of one tensor's optimizer arrays, after checking them."""
+    import torch
+    dt = _grad_out(param, what)
+    for name, t in (("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq), ("master", master)):
+        if t is None and name == "master":
+            continue
+        if t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != param.numel():
+            raise ValueError(f"{what}: {name} must be a contiguous 1-D float32 tensor as long as param")
+        if t.device != param.device:
+            raise ValueError(f"{what}: {name} on a different device than param")
+    if master is not None and dt == STG_DT_F32:
+        raise ValueError(f"{what}: master given beside a float32 param")
+    return dt, (master.data_ptr() if master is not None else None)
+
+
+def _adamw_hyper(step, lr, betas, eps, weight_decay, decoupled) -> StgAdamwHyper:
+    return StgAdamwHyper(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step),
+                         int(bool(decoupled)))
+
+
+def merge_adamw(streams, per_rank: int, param, exp_avg, exp_avg_sq, step: int, lr: float = 1e-3,
+                betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, decoupled: bool = True,
+                master=None):
+    """MERGE decompress and the ``torch.optim.AdamW`` step (``decoupled=False``:
+    ``Adam`` with its L2 term; no amsgrad, no maximize) in ``merge_grad``'s
+    launches: every element's moments decay and every parameter moves, with
+    the averaged gradient ``merge_grad`` would write (+0.0 where no rank
+    wrote), which is never stored.  ``param`` is 1-D float32, bfloat16 or
+    float16; ``exp_avg`` / ``exp_avg_sq`` are float32 of its length and owned
+    by the caller, as is ``master`` (float32, beside a 16-bit ``param``: the
+    step runs on it and ``param`` receives its rounding).  ``step`` counts
+    from 1.  The float32 arrays must share one address phase mod 16 (slices
+    of flat buffers at one offset do).  Returns ``param``."""
+    import torch
+    dt, mp = _adamw_state("merge_adamw", param, exp_avg, exp_avg_sq, master)
+    arr = _rank_streams(streams, per_rank)
+    dev = streams[0][0].device
+    if param.device != dev:
+        raise ValueError("merge_adamw: param on a different device than the streams")
+    hyper = _adamw_hyper(step, lr, betas, eps, weight_decay, decoupled)
+    check(lib().stg_merge_adamw_device(arr, per_rank, len(streams), param.numel(), C.c_void_p(param.data_ptr()), dt,
+                                       C.c_void_p(mp), C.c_void_p(exp_avg.data_ptr()),
+                                       C.c_void_p(exp_avg_sq.data_ptr()), C.byref(hyper),
+                                       C.c_void_p(torch.cuda.current_stream(dev.index).cuda_stream)))
+    return param
+
+
+class AdamWTasks:
+    """A prebuilt ``stg_adamw_task_t`` array for ``merge_adamw_batch``,
+    marshalled and validated once: it holds pointers and sizes only, so it
+    stays valid while ``lr`` and ``step`` change between iterations.  Each
+    item is ``(streams, per_rank, param, exp_avg, exp_avg_sq)`` or the same
+    with ``master`` as a sixth entry, as ``merge_adamw`` takes them.  The
+    array keeps every tensor it points at alive; ``outputs`` holds the items'
+    ``param`` tensors."""
+
+    def __init__(self, items):
+        items = list(items)
+        self.count = len(items)
+        self.array = (StgAdamwTask * max(self.count, 1))()
+        self.device = items[0][0][0][0].device if items and items[0][0] else None
+        self.outputs = []
+        self._keep = []
+        for j, it in enumerate(items):
+            if not 5 <= len(it) <= 6:
+                raise ValueError(f"merge_adamw_batch: item {j}: (streams, per_rank, param, exp_avg, exp_avg_sq"
+                                 "[, master]) expected")
+            streams, per_rank, param, m, v = it[:5]
+            master = it[5] if len(it) == 6 else None
+            per_rank = int(per_rank)
+            try:
+                ranks = _rank_streams(streams, per_rank)
+                dt, mp = _adamw_state("param", param, m, v, master)
+            except ValueError as e:
+                raise ValueError(f"merge_adamw_batch: item {j}: {e}") from None
+            if streams[0][0].device != self.device or param.device != self.device:
+                raise ValueError(f"merge_adamw_batch: item {j}: tensors on different devices")
+            self.array[j] = StgAdamwTask(ranks, per_rank, len(streams), param.numel(), param.data_ptr(), dt, mp,
+                                         m.data_ptr(), v.data_ptr())
+            self._keep.append((ranks, streams, m, v, master))
+            self.outputs.append(param)
+
+
+def merge_adamw_batch(items, step: int, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                      weight_decay: float = 1e-2, decoupled: bool = True):
+    """``merge_adamw`` for many tensors through one C call
+    (``stg_merge_adamw_batch_device``), grouped as ``merge_grad_batch`` groups
+    them; every array is bitwise what the loop leaves.  One set of
+    hyperparameters per call: a model with a decay and a no-decay group makes
+    two calls.  ``items`` as ``AdamWTasks`` takes them, or a prebuilt
+    ``AdamWTasks``.  Returns the items' ``param`` tensors."""
+    import torch
+    tasks = items if isinstance(items, AdamWTasks) else AdamWTasks(items)
+    if not tasks.count:
+        return []
+    hyper = _adamw_hyper(step, lr, betas, eps, weight_decay, decoupled)
+    with torch.cuda.device(tasks.device):
+        rc = lib().stg_merge_adamw_batch_device(
+            tasks.array, tasks.count, C.byref(hyper),
+            C.c_void_p(torch.cuda.current_stream(tasks.device.index).cuda_stream))
     if rc:
         check(rc)
     return tasks.outputs

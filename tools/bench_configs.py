@@ -27,6 +27,9 @@ times the other configs on one GPU and prints one JSON line per measurement:
   MGRAD   (--only merge_grad) merge_grad / merge_grad_batch (the dense typed
       gradient) against today's sequence from public calls: scatter_merge_sparse,
       the count read on the host, zero_(), index_put_ and a cast;
+  MADAMW  (--only merge_adamw) merge_adamw / merge_adamw_batch (the fused dense
+      AdamW step) against merge_grad followed by torch.optim.AdamW, fused and
+      foreach, plus the copy_ into a bf16 parameter where there is a master;
   TVSEND  (--only tvsend) the one-call send path on a threshold-v handle over
       256 tensors against the per-tensor loop, three rotated cycles;
   E2E thresholdv16 64 MiB host-inclusive (serial and overlapped).
@@ -433,6 +436,86 @@ def merge_grad_rows(torch, calls, repeats=5):
             S.merge_grad_batch(pre)
             row["batch_launches"] = S.merge_batch_launches() - before
         yield row
+
+
+def merge_adamw_rows(torch, calls, repeats=5):
+    """MADAMW: the fused dense AdamW step (merge_adamw) beside what runs
+    without it -- merge_grad into a gradient tensor, then torch.optim.AdamW
+    (fused=True; the foreach default as a second column), and for a bf16
+    parameter over an fp32 master the copy_ into the parameter.  Shapes and
+    method as merge_grad_rows: a 64 MiB tensor at worlds 2 and 8, and 256
+    tensors of 60,000 floats at world 8 as a loop, one batched call and a
+    prebuilt batch; medians of `repeats` timed loops between device events.
+    Every timed call rotates over four (64 MiB) or three (256 tensors) copies
+    of the model state, > 512 MB, so the Infinity Cache serves neither side."""
+    import statistics
+    import stellatrain_amd as S
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev)
+    hyp = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2)
+
+    def tensors(n, k, world, count, seed):
+        g = torch.Generator(device="cpu").manual_seed(seed)
+        return [[(torch.sort(torch.randperm(n, generator=g)[:k]).values.to(torch.int32).to(dev),
+                  torch.randn(k, generator=g).to(dev), 0) for _ in range(world)] for _ in range(count)]
+
+    def med(fn, ncalls):
+        return round(statistics.median(_time_loop(torch, st, fn, ncalls, 4 if r == 0 else 0) for r in range(repeats)), 2)
+
+    def models(n, count, master):
+        """Per tensor (param, m, v[, master]) for merge_adamw, and the fp32 tensors torch's optimizers step."""
+        x = [torch.randn(n, device=dev) for _ in range(count)]
+        p = [t.to(torch.bfloat16) for t in x] if master else x
+        mv = [(torch.zeros(n, device=dev), torch.zeros(n, device=dev)) for _ in range(count)]
+        x32 = [t.clone() for t in x]
+        for t in x32:
+            t.grad = torch.zeros_like(t)
+        return [(a,) + b + ((c,) if master else ()) for a, b, c in zip(p, mv, x)], x32
+
+    def today(opt, ts, k, x32, p16):
+        for t, x in zip(ts, x32):
+            S.merge_grad(t, k, x.grad)
+        opt.step()
+        for x, p in zip(x32, p16 or ()):
+            p.copy_(x)
+
+    def baselines(row, ts, k, sets, master, ncalls):
+        """`sets`: the models the timed calls rotate over, so that no call finds its arrays in the Infinity Cache."""
+        for name, kw in (("today_fused_us", {"fused": True}), ("today_foreach_us", {})):
+            opts = [torch.optim.AdamW(x32, **hyp, **kw) for _, x32 in sets]
+            row[name] = med(lambda s: today(opts[s % len(sets)], ts, k, sets[s % len(sets)][1],
+                                            [f[0] for f in sets[s % len(sets)][0]] if master else None), ncalls)
+
+    def step(ts, k, fused, s, master):
+        for t, f in zip(ts, fused):
+            S.merge_adamw(t, k, f[0], f[1], f[2], s + 1, master=f[3] if master else None, **hyp)
+
+    for master in (False, True):
+        name = "bf16 param + fp32 master" if master else "fp32 param"
+        for world in (2, 8):
+            n, k = 16 << 20, S.merge_numel(16 << 20, 0.99)
+            ts = tensors(n, k, world, 1, 7)
+            sets = [models(n, 1, master) for _ in range(4)]  # 4 x 192 MiB of state and more
+            row = {"config": f"MADAMW {name} world={world}, n={n}, k={k} per rank"}
+            baselines(row, ts, k, sets, master, calls)
+            row["merge_adamw_us"] = med(lambda s: step(ts, k, sets[s % 4][0], s, master), calls)
+            yield row
+            del sets
+        n, k, world, count = 60000, 600, 8, 256
+        ts = tensors(n, k, world, count, 11)
+        sets = [models(n, count, master) for _ in range(3)]  # 3 x 184 MB of state and more
+        row = {"config": f"MADAMW {name} {count} x {n} floats, world={world}, k={k} per rank (us per {count} tensors)"}
+        baselines(row, ts, k, sets, master, 3)
+        items = [[(t, k) + f for t, f in zip(ts, fused)] for fused, _ in sets]
+        pre = [S.AdamWTasks(it) for it in items]
+        row["loop_us"] = med(lambda s: step(ts, k, sets[s % 3][0], s, master), 3)
+        row["batch_us"] = med(lambda s: S.merge_adamw_batch(items[s % 3], s + 1, **hyp), 3)
+        row["batch_prebuilt_us"] = med(lambda s: S.merge_adamw_batch(pre[s % 3], s + 1, **hyp), 3)
+        before = S.merge_batch_launches()
+        S.merge_adamw_batch(pre[0], 1, **hyp)
+        row["batch_launches"] = S.merge_batch_launches() - before
+        yield row
+        del sets, items, pre
 
 
 def _time_loop(torch, st, fn, calls, warmup):
@@ -1160,6 +1243,9 @@ def main():
             emit(d)
     if "merge_grad" in only:
         for d in merge_grad_rows(torch, a.calls):
+            emit(d)
+    if "merge_adamw" in only:
+        for d in merge_adamw_rows(torch, a.calls):
             emit(d)
 
 
